@@ -11,14 +11,19 @@ also the RCCL tile gather to rank 0).  Scene parse, BLAS build and upload are
 outside the timed region, like the reference's build_accelerators()
 (reference src/fj_scene_interface.cc:264-270).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --scale 1,2,4,8        # the scaling curve: one compact JSON line per N, then the speed-ups
 
-With N > 1 the line also carries "multi_gpu": one untimed frame taken apart (every rank's render time, the exchange's time)
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds of one timed step, ...).  --dump-outputs DIR writes what the last timed step computed (the
+frame in host memory, its ray counts) as DIR/*.npy; the inputs are seeded, so two builds can be compared output for output.
+Everything else below is measured only with --full.
+
+With N > 1 and --full the line also carries "multi_gpu": one untimed frame taken apart (every rank's render time, the exchange's time)
 and a self-check -- the frame assembled from the N ranks against rank 0's own render of the whole frame.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra
+With --full rank 0's JSON line carries two extra
 objects: "roofline" -- for the kernel that takes the largest share of the frame BY
 MEASURED TIME (HIP events): its HBM traffic from rocprofv3's FETCH_SIZE / WRITE_SIZE
 (calibrated on the walks' own access pattern, profiles/*_fetch_size_calibration.json)
@@ -102,6 +107,14 @@ def parse_args():
                     help="skip the end-to-end leg (the product's bin/scene run as a process of its own on this workload: one cold frame, .fb written)")
     ap.add_argument("--no-pmc", action="store_true",
                     help="skip the rocprofv3 counter passes (HBM traffic, VALU issue) that feed the roofline object")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline figure: the counting frame, "
+                         "the roofline object (rocprofv3 counter passes, gather yardstick), the CPU baselines, the bin/scene end-to-end "
+                         "run and, with N > 1, the frame taken apart with its self-check.  Without it a run sets up, warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy: the frame as rank 0 "
+                         "receives it in host memory (float32) and the whole frame's ray counts by kind, summed over the ranks (float64)")
     return ap.parse_args()
 
 
@@ -239,12 +252,15 @@ def kernel_matcher(kname):
     return match
 
 
+CHILD_FRAMES = 2          # production frames a `--steps 1 --warmup 0` child renders: its cold start + its timed step
+
+
 def pmc_passes(args, kname):
     """Hardware counters of the dominant kernel for THIS build, measured now: one rocprofv3
     --kernel-trace --pmc pass per counter set (FETCH_SIZE and WRITE_SIZE do not fit one pass,
     /opt/skills/guides/MI355X_MICROARCH.md "rocprofv3 PMC slots"; never combined with other
     trace domains), each running this script as a child for ONE timed frame.  Returns
-    {counter: sum over the launches of the production instantiation in that frame} (the child may
+    {counter: sum over the launches of the production instantiation, per frame of the child} (the child may
     cut the frame into another number of launches than the parent: per-frame sums are comparable,
     per-launch ones are not), or None when rocprofv3 is not usable here."""
     import csv
@@ -266,7 +282,9 @@ def pmc_passes(args, kname):
         child += ["--spp"] + [str(v) for v in args.spp]
     if args.device_build:
         child += ["--device-build", str(args.device_build)]
-    env = dict(os.environ, TMPDIR="/tmp", FJGPU_COLD_START="0")       # (ONE production frame in the child: its sums are per frame)
+    env = dict(os.environ, TMPDIR="/tmp", FJGPU_COLD_START="0")       # (whole-frame batches in the child from its first call on)
+    # the child renders CHILD_FRAMES production frames of the same work: its cold start (set-up, outside its timed step) and the
+    # one timed step; the sums below are divided by that count, so that they are per frame
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)                   # (a parent started through the launcher: the counter child is a plain one-GPU run)
     try:
@@ -283,7 +301,7 @@ def pmc_passes(args, kname):
                     out[r["Counter_Name"]] = out.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
                     if r["Counter_Name"] == "SQ_WAVES":
                         out["_launches"] = out.get("_launches", 0.0) + 1.0
-        return out or None
+        return {k: v / CHILD_FRAMES for k, v in out.items()} or None
     except Exception as e:  # noqa: BLE001
         sys.stderr.write("bench: rocprofv3 counter passes failed (%s): roofline.traffic is null\n" % e)
         return None
@@ -355,6 +373,10 @@ def dry_ranks_parent(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.dry_ranks),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.dry_ranks),
            "--steps", str(args.steps), "--warmup", str(args.warmup), "--cpu-tiles", "0", "--no-pmc", "--workload", args.workload]
+    if args.full:
+        cmd += ["--full"]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.mesh:
         cmd += ["--mesh", args.mesh]
     if args.res:
@@ -436,7 +458,8 @@ def scale_parent(args, run=None):
             if a.startswith("--gpus="):
                 continue
             argv.append(a)
-        for flag in ("--no-pmc", "--no-e2e"):
+        # (--full: the N > 1 frame taken apart and its self-check are what a scale point reports)
+        for flag in ("--no-pmc", "--no-e2e", "--full"):
             if flag not in argv:
                 argv.append(flag)
         if "--cpu-tiles" not in argv:
@@ -657,7 +680,13 @@ def main():
         step()
         balance_frames_untimed += 1
     closed = False
-    for _ in range(args.warmup):
+    # the process's cold start (its first frame and, under the default cold-start policy, the frame that grows the work arena) is
+    # set-up: it runs before the timed steps whatever W is, and counts as the first of the W warm-up steps
+    warmup_left = args.warmup
+    if not first:
+        step()
+        warmup_left -= 1
+    for _ in range(warmup_left):
         step()
     sync()
     t0 = time.perf_counter()
@@ -667,19 +696,32 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
 
+    # what the last timed step handed its caller: the frame in host memory (rank 0) and the whole frame's ray counts
+    if args.dump_outputs:
+        counts = torch.tensor([float(getattr(stats[-1].rays, k)) for k in ("camera", "shadow", "diffuse", "reflect", "refract")],
+                              dtype=torch.float64, device=device)
+        if dist.is_initialized():
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM)          # (each rank counts the rays of its own tiles)
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "framebuffer.npy"), host_fb.numpy().astype(np.float32))
+            np.save(os.path.join(args.dump_outputs, "ray_counts.npy"), counts.cpu().numpy())
+
     # One more, UNTIMED frame in the counting instantiation of the traversal kernels: the event
     # counters (nodes / triangles / instance boxes / rays) cost registers and issue slots, so
     # the timed frames run without them.  The frame is deterministic: the counts of this frame
     # are the counts of every timed frame; kernel times come from the timed frames only.
-    gs.set_option("count_nodes", 1)
-    counted = step()
-    sync()
-    gs.set_option("count_nodes", 0)
+    counted = None
+    if args.full:
+        gs.set_option("count_nodes", 1)
+        counted = step()
+        sync()
+        gs.set_option("count_nodes", 0)
 
     # N > 1: one more UNTIMED frame taken apart -- every rank's render on its own clock, then the exchange (pack, gather over RCCL, scatter,
     # the frame's copy to the host) between two barriers: the two numbers a scaling curve is read with (--scale prints them per N)
     multi = None
-    if world > 1:
+    if world > 1 and (args.full or dry):
         sync()
         render_ms = 0.0
         for turn in range(world if dry else 1):          # (--dry-ranks: the ranks share one GPU and render in turns)
@@ -704,7 +746,7 @@ def main():
     # ---------------- aggregate over ranks
     rays_local = float(sum(s.rays.total() for s in stats))
     trace_ms_local = float(sum(s.trace_ms for s in stats))
-    alg_bytes_local = float(algorithmic_bytes(counted, s_node_closest, s_prim, s_node_walk)) * len(stats)
+    alg_bytes_local = float(algorithmic_bytes(counted, s_node_closest, s_prim, s_node_walk)) * len(stats) if counted is not None else 0.0
     launches_local = float(sum(s.trace_launches for s in stats))
     agg = torch.tensor([rays_local, alg_bytes_local, launches_local, elapsed, trace_ms_local], dtype=torch.float64, device=device)
     mx = agg.clone()
@@ -724,154 +766,157 @@ def main():
     if rank == 0:
         s0 = stats[-1]
         per = {k: int(getattr(s0.rays, k)) for k in ("camera", "shadow", "diffuse", "reflect", "refract")}
-        # ---- roofline of the DOMINANT KERNEL on rank 0: the traversal kernel with the largest share of the
-        # frame by MEASURED time (HIP events of exactly its launches in the timed frames)
-        nf = len(stats)
-        shadow_name = "k_shadow_anyhit" if gs.query("lean_anyhit") else ("k_shadow_anyhit_curves" if gs.query("curve_anyhit") else "k_shadow_trace")
-        closest_name = {1: "k_trace_closest_phased", 4: "k_trace_closest_flat"}.get(int(gs.query("closest_kernel")), "k_trace_closest")
-        cand = {
-            shadow_name: {"ms": float(sum(s.shadow_walk_ms for s in stats)), "launches": float(sum(s.shadow_walk_launches for s in stats)),
-                          "alg": float(counted.shadow_nodes * s_node_walk + counted.shadow_prims * s_prim + counted.shadow_insts * S_INST +
-                                       counted.shadow_traversed * S_SHADOW) * nf,
-                          "rays": float(counted.shadow_traversed) * nf,
-                          "streamed_bytes": float(counted.shadow_traversed) * S_SHADOW * nf},
-            closest_name: {"ms": float(sum(s.closest_ms - s.sort_ms for s in stats)), "launches": float(sum(s.closest_launches for s in stats)),
-                           "alg": float(closest_algorithmic_bytes(counted, s_node_closest, s_prim)) * nf,
-                           "rays": float(counted.rays_traced - counted.rays.shadow) * nf,
-                           "streamed_bytes": float(counted.rays_traced - counted.rays.shadow) * S_RAY_IN * nf},
-        }
-        kname = max(cand, key=lambda k: cand[k]["ms"])
-        K = cand[kname]
-        walk_ms, walk_nl, walk_alg = K["ms"], K["launches"], K["alg"]
-        frame_ms_sum = max(1e-9, float(sum(s.total_ms for s in stats)))
-        # the whole traversal side (closest-hit walk + light loop + shadow walk), algorithmic figure only
-        alg = float(algorithmic_bytes(counted, s_node_closest, s_prim, s_node_walk)) * nf
-        tms = float(sum(s.trace_ms for s in stats))
-        nl = float(sum(s.trace_launches for s in stats))
-        # Hardware counters of the SAME build, measured now by rocprofv3 child passes of this script
-        # (pmc_passes): HBM-side traffic = cal x FETCH_SIZE + WRITE_SIZE (both in KB), cal = the factor
-        # scripts/fetch_calibration.py measured on this chip for random 64-byte record gathers
-        # (profiles/r*_fetch_size_calibration.json; MI355X_MICROARCH.md "HBM": calibrate on your own pattern);
-        # VALU issue = ACTIVE_INST_VALU quad-cycles / (SIMDs x elapsed quad-cycles); lane efficiency =
-        # THREAD_CYCLES_VALU / (64 x ACTIVE_INST_VALU).
-        cal = fetch_calibration()
-        traffic, pmc, issue, hbm = None, None, None, None
-        if world == 1 and not args.no_pmc and args.as_rank_of <= 1:
-            # the counter children render the same frame in processes of their own: this process's work arena (110 GB at the headline size)
-            # goes back to the driver first, so that a child finds the memory the timed frames found and cuts its frame into the same batches
-            gs.set_option("release_work", 1)
-            pmc = pmc_passes(args, kname)
-        launches_per_frame = walk_nl / nf if nf else 1.0
-        avg_ms = walk_ms / walk_nl if walk_nl else None
-        if pmc and "TCC_EA0_RDREQ_sum" in pmc and "WRITE_SIZE" in pmc and launches_per_frame and avg_ms:
-            rd, rd32 = pmc["TCC_EA0_RDREQ_sum"], pmc.get("TCC_EA0_RDREQ_32B_sum", 0.0)
-            read_low = 64.0 * (rd - rd32) + 32.0 * rd32            # every request a 64-byte one (= FETCH_SIZE)
-            read_high = 128.0 * (rd - rd32) + 32.0 * rd32          # every request a 128-byte one
-            # coalesced record streams of this kernel per frame (128-byte requests, tallied at 64 B in the lower bound)
-            streamed = K["streamed_bytes"] / nf
-            read_bytes = read_low + min(0.5 * streamed, read_low)
-            how = ("64 B x TCC_EA0_RDREQ (lower bound: right for the 64-byte node gathers, calibrated) + half of the %.1f GB per frame "
-                   "the kernel reads as coalesced streams (128-byte requests)" % (streamed / 1e9))
-            # (per frame in the child -> per launch of this run)
-            traffic = (read_bytes + pmc["WRITE_SIZE"] * 1024.0) / launches_per_frame
-            gbps = traffic / (avg_ms * 1e-3) / 1e9
-            hbm = {"GBps": gbps, "frac_of_peak": gbps / HBM_PEAK_GBPS, "traffic_bytes_per_launch": traffic,
-                   "read_bytes_per_frame": read_bytes, "read_bytes_from": how,
-                   "read_bytes_bounds_per_frame": [read_low, read_high],
-                   "frac_of_peak_bounds": [(read_low + pmc["WRITE_SIZE"] * 1024.0) / launches_per_frame / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                                           min(1.0, (read_high + pmc["WRITE_SIZE"] * 1024.0) / launches_per_frame / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS)],
-                   "read_requests_per_frame": {"all": rd, "32B": rd32},
-                   "launches_in_the_counter_child": pmc.get("_launches"), "launches_per_frame_here": launches_per_frame,
-                   "FETCH_SIZE_KB_per_frame_as_rocprofv3_reports_it": rd * 64.0 / 1024.0, "WRITE_SIZE_KB_per_frame": pmc["WRITE_SIZE"],
-                   "calibration": cal,
-                   "traffic_over_algorithmic": traffic / (walk_alg / walk_nl) if walk_alg else None,
-                   "note": "bytes the L2s requested from the fabric (Infinity Cache hits are in it: an upper bound of DRAM traffic); "
-                           "WRITE_SIZE as reported (uncalibrated; 3 % of this kernel's traffic)"}
-        if pmc and pmc.get("SQ_WAVE_CYCLES") and pmc.get("SQ_WAVES") and pmc.get("SQ_ACTIVE_INST_VALU"):
-            props = torch.cuda.get_device_properties(device)
-            simds = props.multi_processor_count * 4
-            # persistent waves live for the whole launch: wave cycles / waves per launch = the time (in the
-            # counter's own unit) the kernel's launches of one frame were resident, summed over the launches
-            elapsed_q = pmc["SQ_WAVE_CYCLES"] * max(pmc.get("_launches", 1.0), 1.0) / pmc["SQ_WAVES"]
-            # (waves that leave a launch early make elapsed_q an underestimate: the share is capped at 1)
-            busy = min(1.0, pmc["SQ_ACTIVE_INST_VALU"] / (simds * elapsed_q))
-            lane = pmc["SQ_THREAD_CYCLES_VALU"] / (64.0 * pmc["SQ_ACTIVE_INST_VALU"])
-            issue = {"valu_busy": busy, "lane_efficiency": lane, "useful_valu_issue": busy * lane,
-                     "waves_waiting_on_memory": pmc.get("SQ_WAIT_ANY", 0.0) / pmc["SQ_WAVE_CYCLES"],
-                     "waves_stalled_at_issue": pmc.get("SQ_WAIT_INST_ANY", 0.0) / pmc["SQ_WAVE_CYCLES"],
-                     "valu_wave_instructions_per_frame": pmc.get("SQ_INSTS_VALU"), "simds": simds,
-                     "note": "one VALU per SIMD, 4 cycles per wave instruction (FP64 and packed FP32 alike): busy = share of "
-                             "the chip's VALU issue cycles this kernel used, lane_efficiency = active lanes per issued instruction"}
-        # `frac` is a utilisation of a hardware peak measured by counters, <= 1 by construction: the HBM-side
-        # bandwidth of this kernel over the 8 TB/s peak.  Which resource is nearer its roof is said beside it
-        # (`binding_resource`: "valu" when the VALU issue utilisation is the larger fraction).  The algorithmic
-        # bytes of SURVEY 8(d) are reported under `algorithmic` and never priced against the HBM peak.
-        bound, frac, achieved, peak, unit = "hbm", None, None, HBM_PEAK_GBPS, "GB/s"
-        frac_source = "hardware counters (rocprofv3 --pmc child passes of this run)"
-        if hbm:
-            achieved = min(hbm["GBps"], HBM_PEAK_GBPS)
-            frac = achieved / HBM_PEAK_GBPS
-        elif walk_alg and avg_ms:
-            # no counter passes in this run (rocprofv3 missing, --no-pmc, a rank-share run or world > 1): the contract's fields
-            # stay numbers -- an ESTIMATE from this run's algorithmic bytes and the traffic / algorithmic ratio the counters gave
-            # for this kernel family last time they ran (profiles/r03_bench_dragon1080p.json: 0.33) -- and say so
-            traffic = TRAFFIC_OVER_ALGORITHMIC_LAST_MEASURED * walk_alg / walk_nl
-            achieved = min(traffic / (avg_ms * 1e-3) / 1e9, HBM_PEAK_GBPS)
-            frac = achieved / HBM_PEAK_GBPS
-            frac_source = ("UNCALIBRATED estimate: algorithmic bytes of this run x %.2f (the traffic / algorithmic ratio of the last counter run, "
-                           "profiles/r03_bench_dragon1080p.json); the counter passes did not run" % TRAFFIC_OVER_ALGORITHMIC_LAST_MEASURED)
-        # The yardstick for THIS access pattern: the walks gather 64-byte records, and a kernel that does nothing else reaches ~56 G requests/s
-        # (3.5 TB/s) at the scene's footprint on this part, not the 8 TB/s of a stream (profiles/r06_memory_system_notes.txt).  Measured live by the
-        # calibration tool on an array of the scene's size (rounded up to a power of two, >= 256 MiB), and set against the requests the dominant
-        # kernel's L2s sent to the fabric per second (TCC_EA0_RDREQ / launch time).  Reported BESIDE `frac`, which stays the contract's HBM fraction.
-        gather = None
-        if hbm and avg_ms:
-            try:
-                gib = 0.25
-                while gib * (1 << 30) < float(gs.query("scene_bytes")) and gib < 64:
-                    gib *= 2
-                exe = os.path.join(ROOT, "fujiyama-renderer_amd", "bin", "hbm_gather_calib")
-                cj = json.loads(subprocess.run([exe, str(gib), "64"], cwd="/tmp", stdout=subprocess.PIPE, text=True, timeout=120).stdout.strip().splitlines()[-1])
-                ceil_req = cj["kernels"]["k_calib_gather64"]["GBps_needed"] / 64.0            # G requests / s
-                ach_req = hbm["read_requests_per_frame"]["all"] / launches_per_frame / (avg_ms * 1e-3) / 1e9
-                gather = {"achieved_Grequests_per_s": ach_req, "ceiling_Grequests_per_s": ceil_req, "frac_of_gather_ceiling": ach_req / ceil_req,
-                          "calibration_array_GiB": gib, "ceiling_GBps_64B": cj["kernels"]["k_calib_gather64"]["GBps_needed"],
-                          "stream_GBps_same_tool": cj["kernels"]["k_calib_stream"]["GBps_needed"],
-                          "note": "requests past the L2 per second of the dominant kernel against what a pure random 64-byte gather reaches on this GPU at the "
-                                  "scene's footprint (bin/hbm_gather_calib, run now); includes the kernel's coalesced queue reads, so it overstates the gathers"}
-            except Exception as e:  # noqa: BLE001
-                gather = {"error": str(e)}
-        binding = None
-        if issue and frac is not None:
-            binding = "valu" if issue["valu_busy"] > frac else "hbm"
-        roof = {"bound": bound, "achieved": achieved, "peak": peak, "unit": unit, "frac": frac,
-                "traffic": traffic, "traffic_unit": "bytes per launch (fabric side of L2, calibrated FETCH_SIZE + WRITE_SIZE)",
-                "kernel": kname, "launches": int(walk_nl), "avg_launch_ms": avg_ms,
-                "share_of_frame": walk_ms / frame_ms_sum,
-                "picked_by": "largest measured HIP-event time among the traversal kernels",
-                "binding_resource": binding, "frac_source": frac_source, "uncalibrated": hbm is None,
-                "hbm_counters": hbm, "valu_issue": issue, "gather_yardstick": gather,
-                "algorithmic": {"bytes_per_launch": walk_alg / walk_nl if walk_nl else None,
-                                "GBps": walk_alg / (walk_ms * 1e-3) / 1e9 if walk_ms > 0 else None,
-                                "bytes_per_ray": walk_alg / max(1.0, K["rays"]),
-                                "note": "SURVEY 8(d): event counts of this kernel (counting frame) x record sizes = the bytes the walk "
-                                        "must READ; caches serve most of them, so this is data turned over, not an HBM fraction",
-                                "record_bytes": {"node_closest_walk": s_node_closest, "node_shadow_walk": s_node_walk, "tri": s_prim,
-                                                 "instance_box": S_INST, "ray_in": S_RAY_IN, "hit_out": S_HIT_OUT, "shadow_ray": S_SHADOW},
-                                "all_traversal_kernels": {"kernel": closest_name + "+k_shadow_cull+" + shadow_name, "launches": int(nl),
-                                                          "GBps": alg / (tms * 1e-3) / 1e9 if tms > 0 else 0.0,
-                                                          "bytes_per_frame": alg / nf,
-                                                          "bytes_per_ray": alg / max(1.0, float(counted.rays_traced) * nf)}},
-                "kernel_ms_per_frame_rank0": {closest_name: cand[closest_name]["ms"] / nf,
-                                              "ray_sort": float(sum(s.sort_ms for s in stats)) / nf,
-                                              "k_shadow_cull": float(sum(s.light_loop_ms for s in stats)) / nf,
-                                              shadow_name: cand[shadow_name]["ms"] / nf,
-                                              "k_shade": float(sum(s.shade_ms for s in stats)) / nf,
-                                              "k_gen_camera": float(sum(s.gen_ms for s in stats)) / nf,
-                                              "k_resolve": float(sum(s.resolve_ms for s in stats)) / nf}}
+        roof = None
+        if args.full:
+            # ---- roofline of the DOMINANT KERNEL on rank 0: the traversal kernel with the largest share of the
+            # frame by MEASURED time (HIP events of exactly its launches in the timed frames)
+            nf = len(stats)
+            shadow_name = "k_shadow_anyhit" if gs.query("lean_anyhit") else ("k_shadow_anyhit_curves" if gs.query("curve_anyhit") else "k_shadow_trace")
+            closest_name = {1: "k_trace_closest_phased", 4: "k_trace_closest_flat"}.get(int(gs.query("closest_kernel")), "k_trace_closest")
+            cand = {
+                shadow_name: {"ms": float(sum(s.shadow_walk_ms for s in stats)), "launches": float(sum(s.shadow_walk_launches for s in stats)),
+                              "alg": float(counted.shadow_nodes * s_node_walk + counted.shadow_prims * s_prim + counted.shadow_insts * S_INST +
+                                           counted.shadow_traversed * S_SHADOW) * nf,
+                              "rays": float(counted.shadow_traversed) * nf,
+                              "streamed_bytes": float(counted.shadow_traversed) * S_SHADOW * nf},
+                closest_name: {"ms": float(sum(s.closest_ms - s.sort_ms for s in stats)), "launches": float(sum(s.closest_launches for s in stats)),
+                               "alg": float(closest_algorithmic_bytes(counted, s_node_closest, s_prim)) * nf,
+                               "rays": float(counted.rays_traced - counted.rays.shadow) * nf,
+                               "streamed_bytes": float(counted.rays_traced - counted.rays.shadow) * S_RAY_IN * nf},
+            }
+            kname = max(cand, key=lambda k: cand[k]["ms"])
+            K = cand[kname]
+            walk_ms, walk_nl, walk_alg = K["ms"], K["launches"], K["alg"]
+            frame_ms_sum = max(1e-9, float(sum(s.total_ms for s in stats)))
+            # the whole traversal side (closest-hit walk + light loop + shadow walk), algorithmic figure only
+            alg = float(algorithmic_bytes(counted, s_node_closest, s_prim, s_node_walk)) * nf
+            tms = float(sum(s.trace_ms for s in stats))
+            nl = float(sum(s.trace_launches for s in stats))
+            # Hardware counters of the SAME build, measured now by rocprofv3 child passes of this script
+            # (pmc_passes): HBM-side traffic = cal x FETCH_SIZE + WRITE_SIZE (both in KB), cal = the factor
+            # scripts/fetch_calibration.py measured on this chip for random 64-byte record gathers
+            # (profiles/r*_fetch_size_calibration.json: the factor is calibrated on the walks' own access pattern);
+            # VALU issue = ACTIVE_INST_VALU quad-cycles / (SIMDs x elapsed quad-cycles); lane efficiency =
+            # THREAD_CYCLES_VALU / (64 x ACTIVE_INST_VALU).
+            cal = fetch_calibration()
+            traffic, pmc, issue, hbm = None, None, None, None
+            if world == 1 and not args.no_pmc and args.as_rank_of <= 1:
+                # the counter children render the same frame in processes of their own: this process's work arena (110 GB at the headline size)
+                # goes back to the driver first, so that a child finds the memory the timed frames found and cuts its frame into the same batches
+                gs.set_option("release_work", 1)
+                pmc = pmc_passes(args, kname)
+            launches_per_frame = walk_nl / nf if nf else 1.0
+            avg_ms = walk_ms / walk_nl if walk_nl else None
+            if pmc and "TCC_EA0_RDREQ_sum" in pmc and "WRITE_SIZE" in pmc and launches_per_frame and avg_ms:
+                rd, rd32 = pmc["TCC_EA0_RDREQ_sum"], pmc.get("TCC_EA0_RDREQ_32B_sum", 0.0)
+                read_low = 64.0 * (rd - rd32) + 32.0 * rd32            # every request a 64-byte one (= FETCH_SIZE)
+                read_high = 128.0 * (rd - rd32) + 32.0 * rd32          # every request a 128-byte one
+                # coalesced record streams of this kernel per frame (128-byte requests, tallied at 64 B in the lower bound)
+                streamed = K["streamed_bytes"] / nf
+                read_bytes = read_low + min(0.5 * streamed, read_low)
+                how = ("64 B x TCC_EA0_RDREQ (lower bound: right for the 64-byte node gathers, calibrated) + half of the %.1f GB per frame "
+                       "the kernel reads as coalesced streams (128-byte requests)" % (streamed / 1e9))
+                # (per frame in the child -> per launch of this run)
+                traffic = (read_bytes + pmc["WRITE_SIZE"] * 1024.0) / launches_per_frame
+                gbps = traffic / (avg_ms * 1e-3) / 1e9
+                hbm = {"GBps": gbps, "frac_of_peak": gbps / HBM_PEAK_GBPS, "traffic_bytes_per_launch": traffic,
+                       "read_bytes_per_frame": read_bytes, "read_bytes_from": how,
+                       "read_bytes_bounds_per_frame": [read_low, read_high],
+                       "frac_of_peak_bounds": [(read_low + pmc["WRITE_SIZE"] * 1024.0) / launches_per_frame / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                               min(1.0, (read_high + pmc["WRITE_SIZE"] * 1024.0) / launches_per_frame / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS)],
+                       "read_requests_per_frame": {"all": rd, "32B": rd32},
+                       "launches_in_the_counter_child": pmc.get("_launches"), "launches_per_frame_here": launches_per_frame,
+                       "FETCH_SIZE_KB_per_frame_as_rocprofv3_reports_it": rd * 64.0 / 1024.0, "WRITE_SIZE_KB_per_frame": pmc["WRITE_SIZE"],
+                       "calibration": cal,
+                       "traffic_over_algorithmic": traffic / (walk_alg / walk_nl) if walk_alg else None,
+                       "note": "bytes the L2s requested from the fabric (Infinity Cache hits are in it: an upper bound of DRAM traffic); "
+                               "WRITE_SIZE as reported (uncalibrated; 3 % of this kernel's traffic)"}
+            if pmc and pmc.get("SQ_WAVE_CYCLES") and pmc.get("SQ_WAVES") and pmc.get("SQ_ACTIVE_INST_VALU"):
+                props = torch.cuda.get_device_properties(device)
+                simds = props.multi_processor_count * 4
+                # persistent waves live for the whole launch: wave cycles / waves per launch = the time (in the
+                # counter's own unit) the kernel's launches of one frame were resident, summed over the launches
+                elapsed_q = pmc["SQ_WAVE_CYCLES"] * max(pmc.get("_launches", 1.0), 1.0) / pmc["SQ_WAVES"]
+                # (waves that leave a launch early make elapsed_q an underestimate: the share is capped at 1)
+                busy = min(1.0, pmc["SQ_ACTIVE_INST_VALU"] / (simds * elapsed_q))
+                lane = pmc["SQ_THREAD_CYCLES_VALU"] / (64.0 * pmc["SQ_ACTIVE_INST_VALU"])
+                issue = {"valu_busy": busy, "lane_efficiency": lane, "useful_valu_issue": busy * lane,
+                         "waves_waiting_on_memory": pmc.get("SQ_WAIT_ANY", 0.0) / pmc["SQ_WAVE_CYCLES"],
+                         "waves_stalled_at_issue": pmc.get("SQ_WAIT_INST_ANY", 0.0) / pmc["SQ_WAVE_CYCLES"],
+                         "valu_wave_instructions_per_frame": pmc.get("SQ_INSTS_VALU"), "simds": simds,
+                         "note": "one VALU per SIMD, 4 cycles per wave instruction (FP64 and packed FP32 alike): busy = share of "
+                                 "the chip's VALU issue cycles this kernel used, lane_efficiency = active lanes per issued instruction"}
+            # `frac` is a utilisation of a hardware peak measured by counters, <= 1 by construction: the HBM-side
+            # bandwidth of this kernel over the 8 TB/s peak.  Which resource is nearer its roof is said beside it
+            # (`binding_resource`: "valu" when the VALU issue utilisation is the larger fraction).  The algorithmic
+            # bytes of SURVEY 8(d) are reported under `algorithmic` and never priced against the HBM peak.
+            bound, frac, achieved, peak, unit = "hbm", None, None, HBM_PEAK_GBPS, "GB/s"
+            frac_source = "hardware counters (rocprofv3 --pmc child passes of this run)"
+            if hbm:
+                achieved = min(hbm["GBps"], HBM_PEAK_GBPS)
+                frac = achieved / HBM_PEAK_GBPS
+            elif walk_alg and avg_ms:
+                # no counter passes in this run (rocprofv3 missing, --no-pmc, a rank-share run or world > 1): the contract's fields
+                # stay numbers -- an ESTIMATE from this run's algorithmic bytes and the traffic / algorithmic ratio the counters gave
+                # for this kernel family last time they ran (profiles/r03_bench_dragon1080p.json: 0.33) -- and say so
+                traffic = TRAFFIC_OVER_ALGORITHMIC_LAST_MEASURED * walk_alg / walk_nl
+                achieved = min(traffic / (avg_ms * 1e-3) / 1e9, HBM_PEAK_GBPS)
+                frac = achieved / HBM_PEAK_GBPS
+                frac_source = ("UNCALIBRATED estimate: algorithmic bytes of this run x %.2f (the traffic / algorithmic ratio of the last counter run, "
+                               "profiles/r03_bench_dragon1080p.json); the counter passes did not run" % TRAFFIC_OVER_ALGORITHMIC_LAST_MEASURED)
+            # The yardstick for THIS access pattern: the walks gather 64-byte records, and a kernel that does nothing else reaches ~56 G requests/s
+            # (3.5 TB/s) at the scene's footprint on this part, not the 8 TB/s of a stream (profiles/r06_memory_system_notes.txt).  Measured live by the
+            # calibration tool on an array of the scene's size (rounded up to a power of two, >= 256 MiB), and set against the requests the dominant
+            # kernel's L2s sent to the fabric per second (TCC_EA0_RDREQ / launch time).  Reported BESIDE `frac`, which stays the contract's HBM fraction.
+            gather = None
+            if hbm and avg_ms:
+                try:
+                    gib = 0.25
+                    while gib * (1 << 30) < float(gs.query("scene_bytes")) and gib < 64:
+                        gib *= 2
+                    exe = os.path.join(ROOT, "fujiyama-renderer_amd", "bin", "hbm_gather_calib")
+                    cj = json.loads(subprocess.run([exe, str(gib), "64"], cwd="/tmp", stdout=subprocess.PIPE, text=True, timeout=120).stdout.strip().splitlines()[-1])
+                    ceil_req = cj["kernels"]["k_calib_gather64"]["GBps_needed"] / 64.0            # G requests / s
+                    ach_req = hbm["read_requests_per_frame"]["all"] / launches_per_frame / (avg_ms * 1e-3) / 1e9
+                    gather = {"achieved_Grequests_per_s": ach_req, "ceiling_Grequests_per_s": ceil_req, "frac_of_gather_ceiling": ach_req / ceil_req,
+                              "calibration_array_GiB": gib, "ceiling_GBps_64B": cj["kernels"]["k_calib_gather64"]["GBps_needed"],
+                              "stream_GBps_same_tool": cj["kernels"]["k_calib_stream"]["GBps_needed"],
+                              "note": "requests past the L2 per second of the dominant kernel against what a pure random 64-byte gather reaches on this GPU at the "
+                                      "scene's footprint (bin/hbm_gather_calib, run now); includes the kernel's coalesced queue reads, so it overstates the gathers"}
+                except Exception as e:  # noqa: BLE001
+                    gather = {"error": str(e)}
+            binding = None
+            if issue and frac is not None:
+                binding = "valu" if issue["valu_busy"] > frac else "hbm"
+            roof = {"bound": bound, "achieved": achieved, "peak": peak, "unit": unit, "frac": frac,
+                    "traffic": traffic, "traffic_unit": "bytes per launch (fabric side of L2, calibrated FETCH_SIZE + WRITE_SIZE)",
+                    "kernel": kname, "launches": int(walk_nl), "avg_launch_ms": avg_ms,
+                    "share_of_frame": walk_ms / frame_ms_sum,
+                    "picked_by": "largest measured HIP-event time among the traversal kernels",
+                    "binding_resource": binding, "frac_source": frac_source, "uncalibrated": hbm is None,
+                    "hbm_counters": hbm, "valu_issue": issue, "gather_yardstick": gather,
+                    "algorithmic": {"bytes_per_launch": walk_alg / walk_nl if walk_nl else None,
+                                    "GBps": walk_alg / (walk_ms * 1e-3) / 1e9 if walk_ms > 0 else None,
+                                    "bytes_per_ray": walk_alg / max(1.0, K["rays"]),
+                                    "note": "SURVEY 8(d): event counts of this kernel (counting frame) x record sizes = the bytes the walk "
+                                            "must READ; caches serve most of them, so this is data turned over, not an HBM fraction",
+                                    "record_bytes": {"node_closest_walk": s_node_closest, "node_shadow_walk": s_node_walk, "tri": s_prim,
+                                                     "instance_box": S_INST, "ray_in": S_RAY_IN, "hit_out": S_HIT_OUT, "shadow_ray": S_SHADOW},
+                                    "all_traversal_kernels": {"kernel": closest_name + "+k_shadow_cull+" + shadow_name, "launches": int(nl),
+                                                              "GBps": alg / (tms * 1e-3) / 1e9 if tms > 0 else 0.0,
+                                                              "bytes_per_frame": alg / nf,
+                                                              "bytes_per_ray": alg / max(1.0, float(counted.rays_traced) * nf)}},
+                    "kernel_ms_per_frame_rank0": {closest_name: cand[closest_name]["ms"] / nf,
+                                                  "ray_sort": float(sum(s.sort_ms for s in stats)) / nf,
+                                                  "k_shadow_cull": float(sum(s.light_loop_ms for s in stats)) / nf,
+                                                  shadow_name: cand[shadow_name]["ms"] / nf,
+                                                  "k_shade": float(sum(s.shade_ms for s in stats)) / nf,
+                                                  "k_gen_camera": float(sum(s.gen_ms for s in stats)) / nf,
+                                                  "k_resolve": float(sum(s.resolve_ms for s in stats)) / nf}}
         # rays that actually walk a BLAS (camera / reflect / ... closest-hit rays + the shadow rays
         # that survive the instance-box cull), next to the SlTrace-event count of the metric
-        walked = float(sum((s.rays.total() - s.rays.shadow) for s in stats)) + float(counted.shadow_traversed) * nf
+        walked = (float(sum((s.rays.total() - s.rays.shadow) for s in stats)) + float(counted.shadow_traversed) * len(stats)
+                  if counted is not None else None)
         out = {
             "metric": "Mray/s primary+secondary (and ms/frame) at 1920x1080 64spp",
             "value": total_rays / elapsed_max / 1e6,
@@ -886,7 +931,7 @@ def main():
             # ... and its second: the call in which the work arena grows from the cold-start size to the steady-state one (untimed, before the warm-up)
             "second_frame_ms": first.get("second_ms"),
             "peak_hbm_bytes": hbm_use,
-            "traversed_Mray_s": walked / elapsed_max / 1e6 if world == 1 else None,
+            "traversed_Mray_s": walked / elapsed_max / 1e6 if world == 1 and walked is not None else None,
             "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": "%s-class scene, %dx%d, %dx%d spp, tile %dx%d, %d tiles, 32 point lights"
@@ -902,7 +947,7 @@ def main():
                        "prepare_seconds": prep_seconds,
                        "counters_counting_frame_rank0": {"nodes": int(counted.nodes_visited), "prims": int(counted.prims_tested),
                                                          "insts": int(counted.insts_tested), "traced": int(counted.rays_traced),
-                                                         "shadow_traversed": int(counted.shadow_traversed)},
+                                                         "shadow_traversed": int(counted.shadow_traversed)} if counted is not None else None,
                        "ms_last_frame_rank0": {"trace": s0.trace_ms, "shade": s0.shade_ms, "gen": s0.gen_ms,
                                                "resolve": s0.resolve_ms, "total": s0.total_ms,
                                                "ray_sort": s0.sort_ms, "rays_sorted": int(s0.rays_sorted)}},
@@ -992,7 +1037,7 @@ def main():
                                               "projected_frame_ms": max(costs) + tail_ms + xgmi_ms,
                                               "projected_speedup": out["ms_per_step"] / (max(costs) + tail_ms + xgmi_ms),
                                               "slowest_rank_kernels_ms": parts[slow]}
-        if world == 1 and args.cpu_tiles != 0:
+        if world == 1 and args.full and args.cpu_tiles != 0:
             # bounded CPU sample: a block of tiles in the middle of the frame, two tiles per
             # host core (the reference hands whole tiles to its worker threads)
             nx = -(-render.xres // render.tile_w)
@@ -1016,7 +1061,7 @@ def main():
             out["cpu_baseline"]["gpu_ms_same_sample"] = sst.total_ms
             # ... and the restatement (the faster CPU code: no per-ray heap traffic) on a sample with the frame's own mix of tiles
             out["cpu_baseline_port"] = cpu_baseline_port(args, render, scene_ptr, n_tiles)
-        if world == 1 and args.cpu_tiles != 0 and not args.no_e2e and args.as_rank_of <= 1:
+        if world == 1 and args.full and args.cpu_tiles != 0 and not args.no_e2e and args.as_rank_of <= 1:
             gs.close()          # (its ~100 GB of work buffers go back first: the binary is a process of its own on the same GPU)
             closed = True
             out["scene_binary_end_to_end"] = scene_binary_end_to_end(scene_text)

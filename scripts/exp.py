@@ -22,7 +22,7 @@ for spec in sys.argv[2:]:
         if k == "FJGPU_LIBDIR" and not os.path.isabs(v):
             v = os.path.join(root, v)
         env[k] = v
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--cpu-tiles", "0"] + args.split()
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--cpu-tiles", "0"] + args.split()
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     with open(os.path.join(out, "%s.%s.err" % (name, label)), "w") as f:
         f.write(p.stderr)

@@ -28,7 +28,7 @@ def main():
     tmp = tempfile.mkdtemp(prefix="kpmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp", FJGPU_COLD_START="0")
     child = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "1", "--warmup", "0", "--cpu-tiles", "0",
-             "--no-pmc", "--no-e2e"]
+             "--no-pmc", "--no-e2e", "--full"]
     acc = {n: {} for n in names}
     for k, cs in enumerate(SETS):
         d = os.path.join(tmp, "p%d" % k)

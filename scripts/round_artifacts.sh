@@ -10,11 +10,11 @@ bash scripts/prof.sh ${tag}_bench_dragon1080p > $out/${tag}_prof_dragon.log 2>&1
 bash scripts/prof.sh ${tag}_furry1080p --workload furry > $out/${tag}_prof_furry.log 2>&1
 bash scripts/prof.sh ${tag}_cornell1080p --workload cornell > $out/${tag}_prof_cornell.log 2>&1
 bash scripts/prof.sh ${tag}_buddhas720p --workload buddhas > $out/${tag}_prof_buddhas.log 2>&1
-python bench.py --steps 20 --warmup 5 --rank-costs 8 > $out/${tag}_bench_dragon1080p.json 2> $out/${tag}_bench_dragon.err
-python bench.py --workload furry --steps 3 --warmup 1 > $out/${tag}_bench_furry1080p.json 2> $out/${tag}_bench_furry.err
-python bench.py --workload cornell --steps 3 --warmup 1 > $out/${tag}_bench_cornell1080p.json 2> $out/${tag}_bench_cornell.err
-python bench.py --workload buddhas --steps 5 --warmup 2 > $out/${tag}_bench_buddhas720p.json 2> $out/${tag}_bench_buddhas.err
-python bench.py --dry-ranks 8 --steps 1 --warmup 1 > $out/${tag}_bench_dry_ranks8.json 2> $out/${tag}_bench_dry.err
+python bench.py --full --steps 20 --warmup 5 --rank-costs 8 > $out/${tag}_bench_dragon1080p.json 2> $out/${tag}_bench_dragon.err
+python bench.py --full --workload furry --steps 3 --warmup 1 > $out/${tag}_bench_furry1080p.json 2> $out/${tag}_bench_furry.err
+python bench.py --full --workload cornell --steps 3 --warmup 1 > $out/${tag}_bench_cornell1080p.json 2> $out/${tag}_bench_cornell.err
+python bench.py --full --workload buddhas --steps 5 --warmup 2 > $out/${tag}_bench_buddhas720p.json 2> $out/${tag}_bench_buddhas.err
+python bench.py --full --dry-ranks 8 --steps 1 --warmup 1 > $out/${tag}_bench_dry_ranks8.json 2> $out/${tag}_bench_dry.err
 bash scripts/all_workloads.sh > $out/${tag}_all_workloads.txt 2>&1
 for w in buddhas dragon cornell furry ibl; do
   echo "== $w" >> $out/${tag}_full_frame_parity.txt

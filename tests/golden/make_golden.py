@@ -3,13 +3,16 @@
 
 Runs only in the build container (needs oracle/_ref, built from /root/reference by
 `make -C oracle ref`).  Produces
-  tests/golden/ref_vectors.bin   function-level known answers (oracle/ref_vectors.cc)
-  tests/golden/frames.npz        float32 RGBA frames rendered by the reference
+  tests/golden/ref_vectors.bin   function-level known answers (oracle/ref_vectors.cc), committed in
+                                 parts of under 1 MiB (ref_vectors.bin.part00, ...)
+  tests/golden/frames*.npz       float32 RGBA frames rendered by the reference
                                  (oracle/ref_render.cc) for small variants of
                                  BASELINE.json configs C1 (full size), C2, C3
 The scene text and the synthetic assets come from the seeded generators in
 fujiyama-renderer_amd/{workloads,synth}.py, so the tests can rebuild the same
 inputs anywhere.  Fixtures are data only: inputs + expected outputs.
+The reference's other recorded answers (tests/golden/reference_*) are recorded by the tests that use
+them: see tests/reference_records.py.
 """
 import os
 import struct
@@ -24,6 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from fujiyama_renderer_amd import synth, workloads  # noqa: E402
 import edge_scenes  # noqa: E402
+import golden_io  # noqa: E402
 
 REF = os.path.join(ROOT, "oracle", "_ref")
 
@@ -89,6 +93,7 @@ def main():
                    check=True, env=env)
     np.save(os.path.join(HERE, "mesh_trace_rays.npy"), rays)
     print("wrote", out, os.path.getsize(out))
+    golden_io.split_file(out)
 
     frames = {}
     texts = {name: workloads.BUILDERS[builder](asset_dir, **kw) for name, (builder, kw) in list(FRAMES.items()) + list(SERIAL_FRAMES.items())}
@@ -105,8 +110,8 @@ def main():
         w, h, c = struct.unpack("<iii", b[4:16])
         frames[name] = np.frombuffer(b[24:], dtype=np.float32).reshape(h, w, c).copy()
         print(name, frames[name].shape, float(frames[name].mean()))
-    np.savez_compressed(os.path.join(HERE, "frames.npz"), **frames)
-    print("wrote frames.npz", os.path.getsize(os.path.join(HERE, "frames.npz")))
+    golden_io.save_frames(HERE, frames)
+    print("wrote frames*.npz")
 
 
 if __name__ == "__main__":

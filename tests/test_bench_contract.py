@@ -1,4 +1,4 @@
-"""bench.py keeps its output contract: ONE JSON line with the driver's keys, a per-kernel
+"""bench.py keeps its output contract: ONE JSON line with the driver's keys and, with --full, a per-kernel
 `roofline` object and a `cpu_baseline` object (here on the small teapot workload, seconds)."""
 import json
 import os
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "teapot", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "teapot", "--steps", "2", "--warmup", "1", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -52,6 +52,49 @@ def test_bench_line_has_the_contract_fields():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] in ("reference", "port") and c["value"] > 0 and c["cores"] >= 1
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) prints the headline fields only -- no roofline, no CPU baseline -- and --dump-outputs writes the
+    last timed frame as rank 0 receives it plus that frame's ray counts"""
+    out = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "teapot", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "Mray/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["roofline"] is None and "cpu_baseline" not in d and "scene_binary_end_to_end" not in d
+    import numpy as np
+    fb = np.load(str(out / "framebuffer.npy"))
+    rays = np.load(str(out / "ray_counts.npy"))
+    assert fb.dtype == np.float32 and fb.shape == (256, 256, 4) and fb[..., 3].max() > 0 and np.isfinite(fb).all()
+    assert rays.dtype == np.float64 and rays.shape == (5,) and rays[0] >= 256 * 256 and rays.sum() > 0
+    # ray counts of one step times the steps over the timed seconds = the headline rate
+    assert abs(rays.sum() / (d["ms_per_step"] * 1e-3) / 1e6 - d["value"]) <= 1e-6 * d["value"]
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+
+
+@pytest.mark.gpu
+def test_plain_bench_without_warmup_keeps_the_cold_start_out_of_the_timed_steps(tmp_path):
+    """--warmup 0: the process's cold start (first frame, then the frame that grows the work arena) is set-up, reported as
+    first_frame_ms / second_frame_ms, and not one of the timed steps; the headline rate is the timed steps' rays over their time"""
+    out = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "teapot", "--steps", "3", "--warmup", "0",
+                        "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 0 and d["first_frame_ms"] > 0 and d["second_frame_ms"] > 0
+    import numpy as np
+    rays = np.load(str(out / "ray_counts.npy"))
+    assert abs(rays.sum() * d["steps"] / (d["ms_per_step"] * d["steps"] * 1e-3) / 1e6 - d["value"]) <= 1e-6 * d["value"]
+    # were the cold start inside the timed window, the three steps would take longer than the cold start's two frames alone
+    assert d["ms_per_step"] * d["steps"] < d["first_frame_ms"] + d["second_frame_ms"], d
 
 
 @pytest.mark.gpu

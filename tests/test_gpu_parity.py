@@ -163,7 +163,7 @@ def test_frames_match_oracle_and_reference_golden(name, asset_dir, golden_dir):
     builder, kw = CASES[name]
     fb, st, ref, rc = render_both(workloads.BUILDERS[builder](asset_dir, **kw))
     assert_parity(fb, st, ref, rc)
-    golden = np.load(os.path.join(golden_dir, "frames.npz"))[name]   # rendered by the compiled reference
+    golden = golden_io.load_frames(golden_dir)[name]   # rendered by the compiled reference
     assert fb.shape == golden.shape
     assert close_enough(fb, None, golden, None, _last["adaptive"], REL_TOL)
     assert st.nodes_visited > 0 and st.prims_tested > 0 and st.rays_traced == st.rays.total()

@@ -15,6 +15,7 @@ import pytest
 
 import golden_io
 import oracle_ffi
+import reference_records
 from frame_cases import FRAMES as FRAME_CASES
 from fujiyama_renderer_amd import ffi, gpu, host, workloads
 
@@ -266,7 +267,7 @@ def test_oracle_frames_match_reference_renders(name, golden_dir, asset_dir):
     filter.  Reference pixels (captured as raw f32 through the frame-done callback) are
     reproduced BIT-EXACTLY by the restatement."""
     builder, kw = FRAME_CASES[name]
-    frames = np.load(os.path.join(golden_dir, "frames.npz"))
+    frames = golden_io.load_frames(golden_dir)
     host.run_scene_text(workloads.BUILDERS[builder](asset_dir, **kw), deferred=True)
     sp, rd = host.get_desc()
     osc = oracle_ffi.OracleScene(sp)
@@ -298,7 +299,7 @@ def test_oracle_serial_streams_match_one_thread_reference_bit_exactly(name, gold
     seeded, drawn from in the reference's shading order over the whole frame -- reproduces the
     reference frame bit for bit: estimator, weights, depth limits and draw order are all pinned."""
     builder, kw = SERIAL_CASES[name]
-    ref = np.load(os.path.join(golden_dir, "frames.npz"))[name]
+    ref = golden_io.load_frames(golden_dir)[name]
     host.run_scene_text(workloads.BUILDERS[builder](asset_dir, **kw), deferred=True)
     sp, rd = host.get_desc()
     osc = oracle_ffi.OracleScene(sp)
@@ -322,7 +323,7 @@ def test_oracle_edge_case_frames_match_reference_renders(golden_dir, asset_dir):
     """translucent occluders, no shadows, depth limits, colour filter, 0 / 5 / 70 lights,
     diffuse + bump maps, ragged frame + region, no jitter + wide filter, empty scene"""
     import edge_scenes
-    frames = np.load(os.path.join(golden_dir, "frames.npz"))
+    frames = golden_io.load_frames(golden_dir)
     for name, kw in sorted(edge_scenes.EDGE_CASES.items()):
         host.run_scene_text(edge_scenes.custom_scene(asset_dir, **kw), deferred=True)
         sp, rd = host.get_desc()
@@ -343,11 +344,6 @@ def test_oracle_thread_count_invariance(asset_dir):
     assert np.array_equal(a, b) and ra.as_dict() == rb.as_dict()
 
 
-REF_SCENES = "/root/reference/scenes"
-REF_RENDER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "ref_render")
-
-
-@pytest.mark.skipif(not (os.path.isdir(REF_SCENES) and os.path.exists(REF_RENDER)), reason="needs /root/reference and oracle/_ref")
 @pytest.mark.parametrize("scene,mesh", [("teapot", "tiny"), ("happy_buddhas", "tiny"), ("xyzrgb_dragon", "small"), ("furry_bunny", "furball")])
 def test_reference_scene_text_through_the_parser_matches_the_reference_render(scene, mesh, asset_dir, tmp_path):
     """The caller's side of the boundary on the reference's OWN scene text: scenes/<name>.scn --
@@ -355,16 +351,15 @@ def test_reference_scene_text_through_the_parser_matches_the_reference_render(sc
     group assignments verbatim -- with only the asset / output PATHS replaced (the scans and HDR
     maps are not in the image: synthetic meshes and sky) and one line added, a render_region that
     bounds the CPU time (a region only selects tiles).  The unmodified reference renders it
-    (oracle/_ref/ref_render) and writes its .fb; the product's command parser reads the same text
+    (oracle/_ref/ref_render) and writes its .fb (frame and file digest recorded: tests/reference_records.py;
+    the .scn files under tests/golden/reference_scenes/); the product's command parser reads the same text
     (deferred: no GPU here), and the CPU restatement renders the flat description it produced:
     same pixels, bit for bit.  The product's .fb writer, fed the reference's pixels, writes the
     reference's .fb file byte for byte (src/fj_framebuffer_io.cc:46-68)."""
     import re
-    import struct
-    import subprocess
     from fujiyama_renderer_amd import synth
     a = synth.ensure_assets(asset_dir, (mesh,))
-    text = open(os.path.join(REF_SCENES, scene + ".scn")).read()
+    text = reference_records.scene_file(scene)
     text, n_mip = re.subn(r"\S*\.mip\b", a["sky"], text)
     text, n_floor = re.subn(r"\S*/floor\.ply\b", a["floor"], text)
     text, n_dome = re.subn(r"\S*/dome\.ply\b", a["dome"], text)
@@ -377,12 +372,8 @@ def test_reference_scene_text_through_the_parser_matches_the_reference_render(sc
     scn = str(tmp_path / (scene + ".scn"))
     with open(scn, "w") as f:
         f.write(text)
-    env = dict(os.environ, LD_LIBRARY_PATH=os.path.dirname(REF_RENDER))
-    subprocess.run([REF_RENDER, scn, scn + ".fjfb"], check=True, env=env, stdout=subprocess.DEVNULL, timeout=900)
-    with open(scn + ".fjfb", "rb") as f:
-        b = f.read()
-    w, h, c = struct.unpack("<iii", b[4:16])
-    ref = np.frombuffer(b[24:], dtype=np.float32).reshape(h, w, c).copy()
+    ref, ref_fb_sha256 = reference_records.render("scene_text/" + scene, scn, fb_path)
+    h, w, c = ref.shape
     assert (w, h, c) == (640, 480, 4) and ref[192:256, 256:384, 3].max() > 0 and not ref[:192].any()
 
     # the product's parser, same text (its own SaveFrameBuffer goes to another file: in deferred
@@ -397,5 +388,5 @@ def test_reference_scene_text_through_the_parser_matches_the_reference_render(sc
 
     ours = str(tmp_path / "ours.fb")
     assert host.lib().fj_write_fb_file(ours.encode(), w, h, c, ref.ctypes.data_as(C.c_void_p)) == 0
-    assert open(ours, "rb").read() == open(fb_path, "rb").read()
+    assert reference_records.sha256(ours) == ref_fb_sha256
     host.close_scene()

@@ -2,8 +2,9 @@
 
 north_star: "scenes/*.py ... load unchanged".  The reference's emitter
 (tools/python_api/fujiyama.py:137-333) is Python 2 and only formats commands; the build's
-counterpart is fujiyama-renderer_amd/fujiyama.py.  Here the scripts under /root/reference/scenes
-are executed AS THEY ARE with `import fujiyama` resolving to that module, and
+counterpart is fujiyama-renderer_amd/fujiyama.py.  Here the SceneInterface calls the reference's
+scripts make -- recorded from the scripts as they are (tests/reference_records.py) -- are made on
+that module, and
 
   * for the four scenes the reference maintains by hand as `.scn` twins
     (scenes/{happy_buddhas,xyzrgb_dragon,furry_bunny}.scn; teapot.scn has no .py), the emitted
@@ -13,11 +14,10 @@ are executed AS THEY ARE with `import fujiyama` resolving to that module, and
     emits a stream the product's command parser accepts up to the first asset it would read
     (grammar, arity, names, plugin names, property names and types).
 
-Build container only: the scripts are read from /root/reference at test time and nothing of
-them is copied into the repository or travels to the GPU box.
+No script is copied into the repository: the fixtures hold the calls each made, the reference's
+`.scn` files and the frames the compiled reference rendered (tests/golden/reference_*).
 """
 import os
-import runpy
 import sys
 
 import pytest
@@ -25,10 +25,8 @@ import pytest
 from fujiyama_renderer_amd import fujiyama as emitter
 from fujiyama_renderer_amd import host
 
-REF_SCENES = "/root/reference/scenes"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_SCENES), reason="needs the reference tree (build container)")
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import reference_records  # noqa: E402
 
 
 def _write_hdr(path):
@@ -39,15 +37,17 @@ def _write_hdr(path):
 
 
 def run_script(name, tmp_path, monkeypatch, argv=()):
-    """exec scenes/<name>.py with the Py3 emitter as `fujiyama`; returns the emitted text.
-    The script runs in <tmp>/scenes/x so that its relative asset paths (../../hdr/*.hdr) resolve
-    to synthetic stand-ins: NewTexture really converts a .hdr on the way, as the reference's does."""
+    """the calls scenes/<name>.py makes, on the Py3 emitter's SceneInterface (created as the script creates it, with
+    `argv` as its command line); returns the emitted text.  The calls run in <tmp>/scenes/x so that the script's
+    relative asset paths (../../hdr/*.hdr) resolve to synthetic stand-ins: NewTexture really converts a .hdr on the
+    way, as the reference's does."""
     cwd = tmp_path / "scenes" / "x"
     cwd.mkdir(parents=True, exist_ok=True)
-    src = open(os.path.join(REF_SCENES, name + ".py")).read()
+    calls = reference_records.script_calls(name)
     (tmp_path / "hdr").mkdir(exist_ok=True)
     import re
-    for hdr in set(re.findall(r"\.\./\.\./hdr/([\w\-.]+\.hdr)", src)):
+    args = " ".join(str(a) for _, aa in calls for a in aa)
+    for hdr in set(re.findall(r"\.\./\.\./hdr/([\w\-.]+\.hdr)", args)):
         if not (tmp_path / "hdr" / hdr).exists():
             _write_hdr(str(tmp_path / "hdr" / hdr))
     captured = {}
@@ -60,7 +60,9 @@ def run_script(name, tmp_path, monkeypatch, argv=()):
     monkeypatch.setitem(sys.modules, "fujiyama", emitter)
     monkeypatch.setattr(sys, "argv", [name + ".py"] + list(argv))
     monkeypatch.chdir(cwd)
-    runpy.run_path(os.path.join(REF_SCENES, name + ".py"), run_name="__main__")
+    si = emitter.SceneInterface()
+    for method, a in calls:
+        getattr(si, method)(*a)
     assert "text" in captured, "the script never called Run() / Print()"
     return captured["text"]
 
@@ -105,7 +107,7 @@ def same_stream(a, b):
 @pytest.mark.parametrize("name", ["happy_buddhas", "xyzrgb_dragon", "furry_bunny"])
 def test_reference_scripts_emit_their_hand_maintained_scn_twins(name, tmp_path, monkeypatch):
     emitted = normalise(run_script(name, tmp_path, monkeypatch))
-    twin = normalise(open(os.path.join(REF_SCENES, name + ".scn")).read())
+    twin = normalise(reference_records.scene_file(name))
     same_stream(emitted, twin)
     assert len(emitted) > 100 and emitted[-2][0] == "RenderScene" and emitted[-1][0] == "SaveFrameBuffer"
 
@@ -167,7 +169,6 @@ def test_in_scope_reference_scripts_speak_the_products_command_language(name, tm
 # Scene zoo: the in-scope scene scripts of the reference beyond the five BASELINE configurations, with the
 # reference's OWN parameter choices (cameras, lights, transforms and their time samples, shader settings,
 # sampler settings), rendered by the compiled reference and by the product's parser + the CPU restatement.
-REF_RENDER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "ref_render")
 # scripts whose random streams depend on the worker schedule in the reference (PathtracingShader's per-thread
 # generator, the area lights' shared one): pinned through ONE worker thread and the restatement's serial-stream mode
 SERIAL = {"pathtracing", "grid_light", "sphere_light"}
@@ -175,16 +176,14 @@ ZOO = ["bump_mapping", "camera_motion_blur", "dome_light1", "dome_light2", "glas
        "mesh_velocity_blur", "pathtracing", "sphere_light", "teapot2", "transform_motion_blur"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_RENDER), reason="needs oracle/_ref (the compiled reference)")
 @pytest.mark.parametrize("name", ZOO)
 def test_scene_zoo_reference_scripts_render_like_the_reference(name, tmp_path, monkeypatch, asset_dir):
     """scenes/<name>.py as it is -> the Py3 emitter (-R 64 48 -S 2 2) -> only asset paths replaced by synthetic
-    stand-ins -> (a) the unmodified compiled reference renders the stream (oracle/_ref/ref_render), (b) the
+    stand-ins -> (a) the unmodified compiled reference renders the stream (oracle/_ref/ref_render; its frame recorded
+    in tests/golden/reference_frames.npz), (b) the
     product's parser reads the same stream and the CPU restatement renders its flat description: the same
     pixels BIT FOR BIT.  (The GPU suite covers the same features against the restatement on the build's own
     workloads: motion kinds, area lights, dome lights, glass, bump maps, hair with velocities.)"""
-    import struct
-    import subprocess
     import numpy as np
     import oracle_ffi
     from fujiyama_renderer_amd import synth
@@ -234,13 +233,8 @@ def test_scene_zoo_reference_scripts_render_like_the_reference(name, tmp_path, m
     scn = str(tmp_path / (name + ".scn"))
     with open(scn, "w") as f:
         f.write(text)
-    env = dict(os.environ, LD_LIBRARY_PATH=os.path.dirname(REF_RENDER))
-    subprocess.run([REF_RENDER, scn, scn + ".fjfb"], check=True, env=env, stdout=subprocess.DEVNULL, timeout=900)
-    with open(scn + ".fjfb", "rb") as f:
-        b = f.read()
-    w, h, c = struct.unpack("<iii", b[4:16])
-    ref = np.frombuffer(b[24:], dtype=np.float32).reshape(h, w, c).copy()
-    assert (w, h, c) == (64, 48, 4) and ref[..., :3].max() > 0
+    ref, _ = reference_records.render("zoo/" + name, scn)
+    assert ref.shape == (48, 64, 4) and ref[..., :3].max() > 0
     host.run_scene_text(text.replace(fb_path, str(tmp_path / "deferred.fb")), deferred=True)
     sp, rd = host.get_desc()
     osc = oracle_ffi.OracleScene(sp)
