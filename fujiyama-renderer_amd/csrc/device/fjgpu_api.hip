@@ -156,6 +156,9 @@ struct fjgpu_scene {
   long render_calls = 0;           // fjgpu_render_tiles calls that rendered something (the first one sizes its batches for a cold start)
   long count_events;
   long count_all_shadow;
+  // queries "stack_peak" / "stack_peak_closest" / "stack_peak_shadow": the most entries any lane's traversal stack held in the launches of the
+  // last render_* / trace call (counting instantiations only, option count_nodes; 0 without it)
+  unsigned long long stack_peak_closest = 0, stack_peak_shadow = 0;
   // work buffers (lazily sized)
   std::unique_ptr<DeviceBuffers> work;
   size_t work_samples, work_rays;
@@ -986,6 +989,14 @@ int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value)
   if (n == "work_bytes") { *value = (double) (scene->work ? scene->work->bytes : 0); return 0; }
   if (n == "stack_need") { *value = scene->stack_need; return 0; }
   if (n == "blas_nodes") { *value = (double) scene->blas_nodes; return 0; }
+  if (n == "stack_peak") { *value = (double) std::max(scene->stack_peak_closest, scene->stack_peak_shadow); return 0; }
+  if (n == "stack_peak_closest") { *value = (double) scene->stack_peak_closest; return 0; }
+  if (n == "stack_peak_shadow") { *value = (double) scene->stack_peak_shadow; return 0; }
+  // entries a walk keeps in LDS before it goes to the overflow area, by kernel family
+  if (n == "stack_lds") { *value = FJ_STACK_LDS; return 0; }
+  if (n == "stack_lds_anyhit") { *value = FJ_STACK_LDS_ANYHIT; return 0; }
+  if (n == "stack_lds_curves") { *value = FJ_STACK_LDS_CURVES; return 0; }
+  if (n == "stack_lds_min") { *value = FJ_STACK_LDS_MIN; return 0; }
   // 1: shadow rays are walked by k_shadow_anyhit (every occluder opaque, no curves, no motion), 0: by k_shadow_trace
   // 1: shadow rays are walked by k_shadow_anyhit_curves (curve scene, every occluder opaque, no motion, instance level within the curve budget)
   if (n == "curve_anyhit") {
@@ -1275,6 +1286,7 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
   if (const char *why = bad_render(r)) return fail(FJGPU_EINVAL, why);
   HIP_TRY(hipSetDevice(sc->device));
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  sc->stack_peak_closest = sc->stack_peak_shadow = 0;
 
   std::vector<fjgpu::TileRect> all;
   fjgpu::GenerateTiles(*r, &all);
@@ -1763,6 +1775,8 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
     acc.rays_traced += hc.traced;
     acc.shadow_traversed += hc.squeued;
     acc.shadow_nodes += hc.sh_nodes; acc.shadow_prims += hc.sh_prims; acc.shadow_insts += hc.sh_insts;
+    sc->stack_peak_closest = std::max(sc->stack_peak_closest, hc.stack_peak);
+    sc->stack_peak_shadow = std::max(sc->stack_peak_shadow, hc.sh_stack_peak);
     acc.batches++;
     if (sc->batch_fn) {
       // (the stream was synchronised above: the batch's pixels are final in d_fb)
@@ -1995,6 +2009,12 @@ int fjgpu_trace(fjgpu_scene *sc, int group, int n, const double *rays, double *o
     out_ids[2 * i] = h[i].inst;
     out_ids[2 * i + 1] = h[i].inst >= 0 ? h[i].prim : -1;
     if (out_uv) { out_uv[2 * i] = h[i].inst >= 0 ? h[i].u : 0; out_uv[2 * i + 1] = h[i].inst >= 0 ? h[i].v : 0; }
+  }
+  sc->stack_peak_closest = sc->stack_peak_shadow = 0;
+  if (stats || sc->count_events) {
+    DCounters hc;
+    HIP_TRY(hipMemcpy(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost));
+    sc->stack_peak_closest = hc.stack_peak;
   }
   if (stats) {
     std::memset(stats, 0, sizeof(*stats));

@@ -418,6 +418,8 @@ __device__ void traverse_anyhit(const DScene &S, const DShadowRay *squeue, float
             if (nh > 2) push(spa, r2);
             if (nh > 3) push(spa, r3);
           }
+          // (the row of the address-coded stack pointer = the entries on the lane's stack)
+          if (kCount) { const uint32_t row = (spa - ah_base) / (BLOCK * 4u); if (row > lc->stack_peak) lc->stack_peak = row; }
         }
         AH_POSTPONE();
       }
@@ -524,10 +526,11 @@ __global__ void __launch_bounds__(BLOCK, kMulti ? FJ_ANYHIT_MINB_MULTI : FJ_ANYH
 {
   __shared__ alignas(16) uint32_t s_stack[FJ_STACK_LDS_ANYHIT * BLOCK + FJ_ANYHIT_RAY_WORDS * BLOCK];     // (+ the rays: TriFilterRay, or 6 doubles per thread and tmax)
   const uint32_t n = cnt->shadow_count < S.shadow_queue_cap ? cnt->shadow_count : S.shadow_queue_cap;
-  LocalCounters lc = {0, 0, 0};
+  LocalCounters lc = {0, 0, 0, 0};
   traverse_anyhit<kCount, kMulti>(S, squeue, s_accum, tune, n, &cnt->shadow_xcd_head[0][0], s_stack, &lc);
   if (kCount) {
     flush_counters(cnt, lc.nodes, lc.prims, lc.insts, 0, 0);
+    flush_stack_peak(&cnt->sh_stack_peak, lc.stack_peak);
     flush_shadow_walk_counters(cnt, lc.nodes, lc.prims, lc.insts);
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&cnt->squeued, (unsigned long long) n);
   }

@@ -262,6 +262,7 @@ __device__ void traverse_anyhit_curves(const DScene &S, const DShadowRay *squeue
               if (nh > 2) push(spa, r2);
               if (nh > 3) push(spa, r3);
             }
+            if (kCount) { const uint32_t row = (spa - ca_base) / (BLOCK * 4u); if (row > lc->stack_peak) lc->stack_peak = row; }
           }
           if (FJ_CANYHIT_POSTPONE && cur != TRAV_DONE && (cur & FJ_LEAF_FLAG) && pleaf == TRAV_DONE && spa >= ca_row1 && !deep) { pleaf = cur; cur = pop(spa); }
         }
@@ -322,10 +323,11 @@ __global__ void __launch_bounds__(BLOCK, FJ_CANYHIT_MINB) k_shadow_anyhit_curves
   __shared__ double s_inst[InstLdsCurves::WORDS];
   InstLdsCurves::fill(S, s_inst);          // (the launcher picked this kernel because the scene fits)
   const uint32_t n = cnt->shadow_count < S.shadow_queue_cap ? cnt->shadow_count : S.shadow_queue_cap;
-  LocalCounters lc = {0, 0, 0};
+  LocalCounters lc = {0, 0, 0, 0};
   traverse_anyhit_curves<kCount>(S, squeue, s_accum, tune, n, &cnt->shadow_xcd_head[0][0], s_stack, &lc, s_inst);
   if (kCount) {
     flush_counters(cnt, lc.nodes, lc.prims, lc.insts, 0, 0);
+    flush_stack_peak(&cnt->sh_stack_peak, lc.stack_peak);
     flush_shadow_walk_counters(cnt, lc.nodes, lc.prims, lc.insts);
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&cnt->squeued, (unsigned long long) n);
   }

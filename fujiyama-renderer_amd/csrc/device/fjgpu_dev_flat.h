@@ -142,6 +142,7 @@ __device__ void traverse_flat(const DScene &S, Policy &pol, TravTune tune, uint3
             if (nh > 3) stk.push(sp, r3);
             if (nh > 2) stk.push(sp, r2);
             if (nh > 1) stk.push(sp, r1);
+            if (kCount && (uint32_t) sp > lc->stack_peak) lc->stack_peak = (uint32_t) sp;
           }
         }
         FJ_FCYC(1, __ballot(in_now));
@@ -214,10 +215,11 @@ __global__ void __launch_bounds__(BLOCK, FJ_FLAT_MINB) k_trace_closest_flat(DSce
   __syncthreads();
   ClosestPolicy pol;
   pol.S = &S; pol.rays = rays; pol.paths = paths; pol.hits = hits; pol.default_group = S.target_group;
-  LocalCounters lc = {0, 0, 0};
+  LocalCounters lc = {0, 0, 0, 0};
   traverse_flat<kCount, kOne>(S, pol, tune, n, &cnt->trace_xcd_head[0][0], make_stack(s_stack, S.stack_overflow, nullptr, FJ_STACK_LDS_FLAT), &lc, s_inst);
   if (kCount) {
     flush_counters(cnt, lc.nodes, lc.prims, lc.insts, 0, 0);
+    flush_stack_peak(&cnt->stack_peak, lc.stack_peak);
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&cnt->traced, (unsigned long long) n);
   }
 }

@@ -408,7 +408,9 @@ __device__ __forceinline__ bool tri_ray_early(V3 v0, V3 v1, V3 v2, V3 orig, V3 d
 // ----------------------------------------------------------------- traversal
 struct Best { double t, u, v; int inst, prim; };
 
-struct LocalCounters { uint32_t nodes, prims, insts; };
+// stack_peak (counting instantiations only): the most entries the lane's traversal stack held at once -- entries beyond the walk's LDS
+// rows (FJ_STACK_LDS*, fjgpu_types.h) lie in the global overflow area, so a peak above that constant says the area was used
+struct LocalCounters { uint32_t nodes, prims, insts, stack_peak; };
 
 // sum over the 64 lanes of the wave (butterfly; every lane gets the total)
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
@@ -435,6 +437,13 @@ __device__ __forceinline__ void flush_counters(DCounters *cnt, unsigned long lon
     if (traced) atomicAdd(&cnt->traced, traced);
     if (shadow) atomicAdd(&cnt->rays[CXT_SHADOW_RAY], shadow);
   }
+}
+
+// the deepest traversal stack of the launch (LocalCounters.stack_peak): the wave's maximum, one atomic per wave
+__device__ __forceinline__ void flush_stack_peak(unsigned long long *peak, uint32_t v)
+{
+  for (int off = 32; off > 0; off >>= 1) { const uint32_t o = __shfl_xor(v, off); v = o > v ? o : v; }
+  if (__lane_id() == 0 && v) atomicMax(peak, (unsigned long long) v);
 }
 
 // the shadow walk's events, counted a second time on their own (per-kernel roofline)

@@ -465,10 +465,11 @@ __global__ void __launch_bounds__(BLOCK, kMotion ? FJ_MOTION_MINB : (kCurves ? F
   const uint32_t n = cnt->shadow_count;         // written by k_shadow_cull earlier on this stream
   ShadowPolicy pol;
   pol.S = &S; pol.squeue = squeue; pol.s_accum = s_accum;
-  LocalCounters lc = {0, 0, 0};
+  LocalCounters lc = {0, 0, 0, 0};
   traverse_persistent<kCurves, kCount, kMotion, kInstLds, kAnyOnly>(S, pol, tune, n, &cnt->shadow_xcd_head[0][0], make_stack(s_stack, S.stack_overflow_shadow, kCurves ? s_rayspace : nullptr), &lc, s_inst);
   if (kCount) {
     flush_counters(cnt, lc.nodes, lc.prims, lc.insts, 0, 0);
+    flush_stack_peak(&cnt->sh_stack_peak, lc.stack_peak);
     flush_shadow_walk_counters(cnt, lc.nodes, lc.prims, lc.insts);
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&cnt->squeued, (unsigned long long) n);
   }

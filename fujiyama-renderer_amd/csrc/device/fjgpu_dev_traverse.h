@@ -429,6 +429,7 @@ __device__ void traverse_persistent(const DScene &S, Policy &pol, TravTune tune,
           if (nh > 3) stk.push(sp, r3);
           if (nh > 2) stk.push(sp, r2);
           if (nh > 1) stk.push(sp, r1);
+          if (kCount && (uint32_t) sp > lc->stack_peak) lc->stack_peak = (uint32_t) sp;
         }
       }
     }
@@ -755,6 +756,7 @@ __device__ void traverse_phased(const DScene &S, Policy &pol, TravTune tune, uin
             if (nh > 3) stk.push(sp, r3);
             if (nh > 2) stk.push(sp, r2);
             if (nh > 1) stk.push(sp, r1);
+            if (kCount && (uint32_t) sp > lc->stack_peak) lc->stack_peak = (uint32_t) sp;
           }
         }
         FJ_PCYC(1, __ballot(in_now));
@@ -854,10 +856,11 @@ __global__ void __launch_bounds__(BLOCK, kMotion ? FJ_MOTION_MINB : (kCurves ? F
   if (kInstLds) InstLdsOf<kCurves>::T::fill(S, s_inst);
   ClosestPolicy pol;
   pol.S = &S; pol.rays = rays; pol.paths = paths; pol.hits = hits; pol.default_group = S.target_group;
-  LocalCounters lc = {0, 0, 0};
+  LocalCounters lc = {0, 0, 0, 0};
   traverse_persistent<kCurves, kCount, kMotion, kInstLds, false>(S, pol, tune, n, &cnt->trace_xcd_head[0][0], make_stack(s_stack, S.stack_overflow, kCurves ? s_rayspace : nullptr), &lc, s_inst);
   if (kCount) {
     flush_counters(cnt, lc.nodes, lc.prims, lc.insts, 0, 0);
+    flush_stack_peak(&cnt->stack_peak, lc.stack_peak);
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&cnt->traced, (unsigned long long) n);
   }
 }
@@ -880,10 +883,11 @@ __global__ void __launch_bounds__(BLOCK, FJ_PHASED_MINB) k_trace_closest_phased(
   if (kInstLds) InstLds::fill(S, s_inst);         // (the launcher picked this instantiation because the scene fits)
   ClosestPolicy pol;
   pol.S = &S; pol.rays = rays; pol.paths = paths; pol.hits = hits; pol.default_group = S.target_group;
-  LocalCounters lc = {0, 0, 0};
+  LocalCounters lc = {0, 0, 0, 0};
   traverse_phased<kCount, false, kInstLds>(S, pol, tune, n, &cnt->trace_xcd_head[0][0], make_stack(s_stack, S.stack_overflow, nullptr, FJ_STACK_LDS), &lc, s_inst);
   if (kCount) {
     flush_counters(cnt, lc.nodes, lc.prims, lc.insts, 0, 0);
+    flush_stack_peak(&cnt->stack_peak, lc.stack_peak);
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&cnt->traced, (unsigned long long) n);
   }
 }

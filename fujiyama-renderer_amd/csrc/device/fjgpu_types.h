@@ -389,7 +389,8 @@ struct DCounters {
   unsigned long long rays[5];  // per context (fj_ray_counts order: camera shadow diffuse reflect refract)
   unsigned long long nodes, prims, insts, traced, squeued;
   unsigned long long sh_nodes, sh_prims, sh_insts;   // the shadow walk's share of nodes / prims / insts
-  unsigned long long pad0_[3];
+  unsigned long long stack_peak, sh_stack_peak;      // counting instantiations: most stack entries a lane held, closest-hit / shadow walks (atomicMax)
+  unsigned long long pad0_[1];
   uint32_t next_count;         // entries appended to the next ray queue                      (line 1)
   uint32_t light_count;        // entries appended to the light-record queue
   uint32_t overflow;

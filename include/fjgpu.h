@@ -216,7 +216,10 @@ int fjgpu_host_instance_level(const fj_scene_desc *desc, int group, int32_t *out
  * 2 its curve instantiation, 3 its motion instantiation, 4 k_trace_closest_flat: one world-space tree per group), "closest_node_record_bytes" (64: the closest-hit walk reads the
  * quantised nodes too; 128 in scenes with curve sets or motion), "has_curves", "has_motion", "scene_bytes" (device memory of the
  * resident scene: BLAS, instance level, lights, textures), "work_bytes" (the wavefront work arena -- queues, accumulators -- as the
- * largest call so far sized it; scene_bytes + work_bytes = the HBM this scene holds).  Returns 0 or FJGPU_EINVAL. */
+ * largest call so far sized it; scene_bytes + work_bytes = the HBM this scene holds), "stack_peak" (with option count_nodes on: the most
+ * entries any lane's traversal stack held in the launches of the last render_* / trace call -- "stack_peak_closest" / "stack_peak_shadow": of the
+ * closest-hit / the shadow walks alone; 0 without the option), "stack_lds" / "stack_lds_anyhit" / "stack_lds_curves" / "stack_lds_min" (entries
+ * the walks keep in LDS: a peak above a walk's figure went through the global overflow area).  Returns 0 or FJGPU_EINVAL. */
 int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value);
 
 /* Diagnostics: the host-side math that feeds geometry to the device (matrices,

@@ -436,14 +436,20 @@ def test_si_render_scene_end_to_end(asset_dir):
     assert st.rays.as_dict() == rc.as_dict() and st.render_seconds > 0
 
 
-@pytest.mark.parametrize("mode", [1, 2], ids=["clustering", "radix_tree"])
-def test_device_blas_build_gives_the_same_hits_and_pixels(asset_dir, golden_dir, mode):
+@pytest.mark.parametrize("mode,ploc_top", [(1, None), (2, None), (1, "1")], ids=["clustering", "radix_tree", "clustering_rounds_to_the_root"])
+def test_device_blas_build_gives_the_same_hits_and_pixels(asset_dir, golden_dir, mode, ploc_top, monkeypatch):
     """BLAS built on the device (fjgpu_lbvh.hip: locally-ordered clustering, or the radix tree of
     the Morton codes) instead of the host's binned-SAH tree: closest hits do not depend on the
     culling structure, so t / ids stay bit-exact against the reference grid vectors and a frame
-    matches the oracle."""
+    matches the oracle.  (Below 65 536 triangles the clustering runs no round by default -- the tree is the
+    host's top tree over the leaves --; the third id sets FJGPU_PLOC_TOP=1, which the builder reads when the
+    scene is created, so that the rounds run down to the root.)"""
     import test_oracle_golden as tg
     vec = golden_io.read_vectors(os.path.join(golden_dir, "ref_vectors.bin"))
+    if ploc_top is None:
+        monkeypatch.delenv("FJGPU_PLOC_TOP", raising=False)
+    else:
+        monkeypatch.setenv("FJGPU_PLOC_TOP", ploc_top)
     gpu.global_option("device_build", mode)
     try:
         sp, _ = prepare(tg._mesh_scene(asset_dir))
