@@ -209,6 +209,10 @@ struct fjgpu_scene {
   int stack_need;
   double tri_record_bytes;         // 36 when every mesh is stored as f32 triangles, else 72
   size_t blas_nodes;
+  // SAH treelet restructuring (fjgpu_lbvh.hip), summed over the device-built meshes of the scene
+  long blas_treelet_passes = 0;
+  unsigned long long blas_treelets_changed = 0;
+  double blas_sah_cost_initial = 0., blas_sah_cost = 0.;
   size_t squeue_max;               // shadow-queue entries allowed by the memory budget
   size_t batch_fit_samples = 0;    // 0, or the samples per batch the work buffers were cut down to when an allocation failed (not tried beyond again)
   // ray-queue sort (fjgpu_raysort.hip): levels >= 1 of scenes with incoherent secondary rays
@@ -409,6 +413,7 @@ static long g_curve_anyhit = 1;    // "curve_anyhit": curve scenes whose occlude
 static long g_inst_lds = 1;        // "inst_lds": the walks keep the instance level of scenes that fit their budget in LDS (DInstEntry)
 static long g_batch_tiles = 0;     // "batch_tiles": default of the per-scene option of that name for scenes created from now on (0 = by memory)
 static long g_device_build = -1;   // "device_build": BLAS of meshes built on the GPU (fjgpu_lbvh.hip): 1 = clustering, 2 = radix tree; 0 = on the host; -1 = not set
+static long g_treelet_passes = 0;  // "blas_treelet_passes": 0 .. 8 passes of SAH treelet restructuring over a device-built BLAS (0 = off: today's trees)
 static long g_multi_exchange = 0;  // "multi_exchange": how fjgpu_render_frame_multi moves the devices' tile slabs: 0 one hipMemcpyPeer each, 1 RCCL grouped send / recv
 static long g_spec_walk = 1;       // "speculative_walk": the next recursion level's closest-hit walk is enqueued before the host has read how many rays it has (the walk reads the count itself)
 static long g_cold_start = 1;      // "cold_start": a scene's first render call uses batches of FJ_COLD_BATCH_SAMPLES samples (a small arena: a fast first frame)
@@ -437,6 +442,7 @@ int fjgpu_global_option(const char *name, long value)
   if (std::string(name) == "compact_squeue") { g_compact_squeue = value != 0; return 0; }
   if (std::string(name) == "batch_tiles") { g_batch_tiles = value < 0 ? 0 : value; return 0; }
   if (std::string(name) == "device_build") { g_device_build = value < 0 ? -1 : (value > 2 ? 2 : value); return 0; }
+  if (std::string(name) == "blas_treelet_passes") { g_treelet_passes = value < 0 ? 0 : (value > 8 ? 8 : value); return 0; }
   if (std::string(name) == "single_frame_build") { g_single_frame = value != 0; return 0; }
   if (std::string(name) == "speculative_walk") { g_spec_walk = value != 0; return 0; }
   if (std::string(name) == "anyhit_filter_off") { set_anyhit_filter_off(value); return 0; }
@@ -537,13 +543,15 @@ static int upload_scene(const fj_scene_desc *desc, fjgpu::HostScene &hs, int dev
         const auto tb0 = std::chrono::steady_clock::now();
         LbvhOut lo;
         std::string lerr;
-        if (LbvhBuildMesh(d.P, d.velocity, d.indices, m.n_faces, m.n_points, h.bounds, h.f32_exact, hs.device_build_quality, &lo, &lerr))
+        if (LbvhBuildMesh(d.P, d.velocity, d.indices, m.n_faces, m.n_points, h.bounds, h.f32_exact, hs.device_build_quality, hs.device_build_treelet_passes, &lo, &lerr))
           return fail(FJGPU_ENODEV, lerr);
         for (void *p : {(void *) lo.nodes, (void *) lo.prim_ids, (void *) lo.tri_verts, (void *) lo.tri_verts32, (void *) lo.tri_vel})
           if (p) M.ptrs.push_back(p);
         d.nodes = lo.nodes; d.prim_ids = lo.prim_ids; d.root = lo.root;
         d.tri_verts = lo.tri_verts; d.tri_verts32 = lo.tri_verts32; d.tri_vel = lo.tri_vel;
         hs.primsets[i].stack_need = lo.stack_need;
+        sc->blas_treelet_passes += lo.treelet_passes; sc->blas_treelets_changed += lo.treelets_changed;
+        sc->blas_sah_cost_initial += lo.sah_cost_initial; sc->blas_sah_cost += lo.sah_cost;
         hs.primsets[i].nodes.n = lo.n_nodes;
         if (lo.tri_verts32) hs.primsets[i].tri_verts32.resize(1);      // (layout flags read below)
         if (lo.tri_vel) hs.primsets[i].tri_vel.resize(1);
@@ -910,6 +918,9 @@ static int build_host_scene(const fj_scene_desc *desc, fjgpu::HostScene *hs)
   if (const char *e = getenv("FJGPU_DEVICE_BUILD")) device_mode = std::max(0, std::min(2, atoi(e)));
   const bool device_build = device_mode != 0;
   hs->device_build_quality = device_mode == 2 ? 0 : 1;
+  long passes = g_treelet_passes;
+  if (const char *e = getenv("FJGPU_TREELET_PASSES")) passes = std::max(0, std::min(8, atoi(e)));
+  hs->device_build_treelet_passes = (int) passes;
   const int be = fjgpu::BuildHostScene(desc, hs, &err, device_build);
   if (getenv("FJGPU_VERBOSE"))
     fprintf(stderr, "fjgpu: host scene build (BLAS, transforms, lights) %.3f s\n",
@@ -989,6 +1000,10 @@ int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value)
   if (n == "work_bytes") { *value = (double) (scene->work ? scene->work->bytes : 0); return 0; }
   if (n == "stack_need") { *value = scene->stack_need; return 0; }
   if (n == "blas_nodes") { *value = (double) scene->blas_nodes; return 0; }
+  if (n == "blas_treelet_passes") { *value = (double) scene->blas_treelet_passes; return 0; }
+  if (n == "blas_treelets_changed") { *value = (double) scene->blas_treelets_changed; return 0; }
+  if (n == "blas_sah_cost_initial") { *value = scene->blas_sah_cost_initial; return 0; }
+  if (n == "blas_sah_cost") { *value = scene->blas_sah_cost; return 0; }
   if (n == "stack_peak") { *value = (double) std::max(scene->stack_peak_closest, scene->stack_peak_shadow); return 0; }
   if (n == "stack_peak_closest") { *value = (double) scene->stack_peak_closest; return 0; }
   if (n == "stack_peak_shadow") { *value = (double) scene->stack_peak_shadow; return 0; }

@@ -61,6 +61,7 @@ struct HostScene {
   std::vector<DAreaLight> area_lights;        // [n_lights] when any rectangle / sphere light exists
   int n_meshes;
   int device_build_quality;                   // fjgpu_lbvh.hip: 0 radix tree, 1 locally-ordered clustering
+  int device_build_treelet_passes = 0;        // fjgpu_lbvh.hip: passes of SAH treelet restructuring over either (0 = none)
   int target_group;
   double cam_M[12];
   double cam_fov, cam_znear, cam_zfar;

@@ -16,6 +16,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -78,8 +79,8 @@ struct BTree {
   uint32_t *left, *right;    // [2n-1], inner entries used
   uint32_t *count;           // [2n-1] leaves below
   Box6 *box;                 // [2n-1]
-  uint32_t *parent;          // [2n-1] (radix-tree path only)
-  int *flag;                 // [n]    (radix-tree path only)
+  uint32_t *parent;          // [2n-1] (the radix tree's own; derived by k_parents for the others)
+  int *flag;                 // [n]    arrival counters of the bottom-up walks
 };
 
 __global__ void __launch_bounds__(LB) k_leaf_nodes(const Box6 *boxes, const uint32_t *vals, int n, BTree T)
@@ -245,6 +246,228 @@ __global__ void __launch_bounds__(LB) k_ploc_apply(const uint32_t *C, int c, con
   Cout[pos] = p;
 }
 
+// ---- SAH treelet restructuring (Karras & Aila 2013), between tree formation and the collapse.  One pass = one launch that walks
+// the binary tree bottom-up with k_fit's arrival counters (the first thread to reach a node returns, the second goes on: nobody
+// waits for anybody).  On arriving at a node of >= 7 leaves the walk forms a TREELET -- the node's two children, then the treelet
+// leaf of largest area that is an inner node opened until there are 7 -- and finds the cheapest binary tree over those 7 by dynamic
+// programming over the 127 non-empty leaf subsets.  The cost is the model becomes_leaf applies, so the pass and the collapse agree:
+//   C(triangle) = A,   C(inner) = min(trav * A + C(l) + C(r),  A * count where count <= FJ_MAX_LEAF_PRIMS),   A = half_area.
+// The five interior node ids of the treelet are reused for the new topology; its root keeps id, box and count; nothing outside changes.
+//
+// DETERMINISM: when a walk arrives at a node everything below it is final and nothing else touches that subtree, so what is done
+// at the node is a function of the subtree alone, not of which wave came first.  The partitions of a subset are enumerated in a
+// fixed order and replace the best so far only when strictly cheaper; the existing topology is the incumbent and is replaced only
+// when the optimum is strictly cheaper IN THE SAME f32 ARITHMETIC (sah_node_cost, children added first: commutative) -- the
+// subset sums of the existing topology are among the DP's candidates bit for bit, so an unchanged optimum rewrites nothing.
+#define TL_LEAVES 7
+#define TL_SETS 128
+#define TL_WAVES (LB / 64)
+#define NO_NODE 0xffffffffu
+
+__device__ __forceinline__ float sah_node_cost(float trav, float area, float kids, uint32_t count)
+{
+  float c = trav * area + kids;
+  if (count <= (uint32_t) FJ_MAX_LEAF_PRIMS) c = fminf(c, area * (float) count);
+  return c;
+}
+
+// the clustering path and the host-built top keep no parents: derived from left / right of the n - 1 inner nodes (ids n .. 2n - 2)
+__global__ void __launch_bounds__(LB) k_parents(int n, uint32_t root2, BTree T)
+{
+  const int i = blockIdx.x * LB + threadIdx.x;
+  if (i >= n - 1) return;
+  const uint32_t p = (uint32_t) (n + i);
+  T.parent[T.left[p]] = p;
+  T.parent[T.right[p]] = p;
+  if (p == root2) T.parent[p] = NO_NODE;
+}
+
+// LDS of one wave: the DP tables (two subsets per lane), the 7 treelet leaves, and per lane the treelet it found at its node
+struct TreeletLds {
+  float copt[TL_SETS];                  // cheapest cost of a subtree over the subset
+  float area[TL_SETS];                  // half area of the subset's union box
+  uint8_t part[TL_SETS];                // one side of the cheapest partition (the side without the subset's lowest leaf)
+  Box6 box[TL_LEAVES];
+  float c[TL_LEAVES];
+  uint32_t cnt[TL_LEAVES];
+  uint32_t ids[64][13];                 // [lane]: 7 leaves, 5 interior nodes (odd stride: lanes on different banks)
+  float open_area[64][TL_LEAVES];       // [lane]: half area of a treelet leaf that can be opened, -1 for a triangle
+  uint32_t stack[TL_LEAVES][2];         // write-back: (subset, node id)
+};
+
+// LDS written by some lanes of a wave and read by others of the SAME wave: the wave runs in lockstep and its DS operations
+// complete in order, so this only has to keep the compiler from moving accesses across
+__device__ __forceinline__ void wave_sync()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ void __launch_bounds__(LB) k_treelet_pass(int n, BTree T, float *C, float trav, unsigned long long *changed)
+{
+  __shared__ TreeletLds lds[TL_WAVES];
+  TreeletLds &L = lds[threadIdx.x >> 6];
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * LB + threadIdx.x;
+  bool active = i < n;
+  uint32_t p = active ? T.parent[i] : NO_NODE;
+  if (p == NO_NODE) active = false;
+  unsigned n_changed = 0;                         // (lane 0 writes back for the whole wave)
+  while (__any(active)) {
+    // arrival: what this wave wrote below p is released before the counter is touched, what the other side wrote is acquired after
+    __threadfence();
+    if (active && atomicAdd(&T.flag[p - (uint32_t) n], 1) == 0) active = false;
+    __threadfence();
+    float c = 0.f;
+    bool want = false;
+    if (active) {
+      const uint32_t l = T.left[p], r = T.right[p], cnt = T.count[p];
+      const float cl = l < (uint32_t) n ? half_area(T.box[l]) : C[l - (uint32_t) n];
+      const float cr = r < (uint32_t) n ? half_area(T.box[r]) : C[r - (uint32_t) n];
+      c = sah_node_cost(trav, half_area(T.box[p]), cl + cr, cnt);
+      C[p - (uint32_t) n] = c;
+      if (cnt >= (uint32_t) TL_LEAVES) {
+        // the treelet under p: open the largest inner leaf until there are 7 (count >= 7: there always is one to open)
+        uint32_t *ids = L.ids[lane];
+        float *oa = L.open_area[lane];
+        ids[0] = l; ids[1] = r;
+        oa[0] = l < (uint32_t) n ? -1.f : half_area(T.box[l]);
+        oa[1] = r < (uint32_t) n ? -1.f : half_area(T.box[r]);
+        int k = 2;
+        while (k < TL_LEAVES) {
+          int pick = -1;
+          float best = -1.f;
+          for (int j = 0; j < k; j++)
+            if (oa[j] > best) { best = oa[j]; pick = j; }
+          if (pick < 0) break;                    // (areas that do not compare: the subtree is left alone)
+          const uint32_t q = ids[pick], ql = T.left[q], qr = T.right[q];
+          ids[TL_LEAVES + k - 2] = q;
+          ids[pick] = ql; ids[k] = qr;
+          oa[pick] = ql < (uint32_t) n ? -1.f : half_area(T.box[ql]);
+          oa[k] = qr < (uint32_t) n ? -1.f : half_area(T.box[qr]);
+          k++;
+        }
+        want = k == TL_LEAVES;
+      }
+    }
+    // the lanes that hold a treelet root, served by the whole wave one after the other
+    unsigned long long todo = __ballot(want);
+    while (todo) {
+      const int src = __ffsll((long long) todo) - 1;
+      todo &= todo - 1;
+      const uint32_t root = (uint32_t) __shfl((int) p, src);
+      const float c_now = __shfl(c, src);
+      const uint32_t *ids = L.ids[src];
+      wave_sync();
+      if (lane < TL_LEAVES) {
+        const uint32_t id = ids[lane];
+        const Box6 b = T.box[id];
+        L.box[lane] = b;
+        L.cnt[lane] = T.count[id];
+        L.c[lane] = id < (uint32_t) n ? half_area(b) : C[id - (uint32_t) n];
+      }
+      wave_sync();
+      // subsets lane and lane + 64: union box, leaf count; a single leaf costs what its subtree costs
+      uint32_t cnt[2] = {0u, 0u};
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int s = lane + 64 * h;
+        if (s == 0) continue;
+        const int first = __ffs(s) - 1;
+        Box6 b = L.box[first];
+        uint32_t m = L.cnt[first];
+        for (int j = first + 1; j < TL_LEAVES; j++)
+          if (s >> j & 1) { b = box_union(b, L.box[j]); m += L.cnt[j]; }
+        L.area[s] = s == TL_SETS - 1 ? half_area(T.box[root]) : half_area(b);    // (the root keeps its box)
+        cnt[h] = m;
+        if (__popc(s) == 1) L.copt[s] = L.c[first];
+      }
+      wave_sync();
+      // rounds by subset size; the partitions of s: q runs over the non-empty subsets of s without its lowest leaf, downwards
+      for (int k = 2; k <= TL_LEAVES; k++) {
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const int s = lane + 64 * h;
+          if (__popc(s) != k) continue;
+          const int rest = s & (s - 1);
+          int q = rest, bq = rest;
+          float best = L.copt[s ^ q] + L.copt[q];
+          for (q = (q - 1) & rest; q; q = (q - 1) & rest) {
+            const float kids = L.copt[s ^ q] + L.copt[q];
+            if (kids < best) { best = kids; bq = q; }
+          }
+          L.copt[s] = sah_node_cost(trav, L.area[s], best, cnt[h]);
+          L.part[s] = (uint8_t) bq;
+        }
+        wave_sync();
+      }
+      if (L.copt[TL_SETS - 1] < c_now) {
+        if (lane == 0) {
+          // write-back: the new topology on the five interior ids, handed out in the order the subsets are visited
+          int sp = 0, next = 0;
+          L.stack[0][0] = TL_SETS - 1; L.stack[0][1] = root; sp = 1;
+          while (sp > 0) {
+            sp--;
+            const uint32_t s = L.stack[sp][0], id = L.stack[sp][1];
+            const uint32_t side[2] = {s ^ (uint32_t) L.part[s], (uint32_t) L.part[s]};
+            uint32_t kid[2];
+            for (int e = 0; e < 2; e++) {
+              if (__popc(side[e]) == 1) kid[e] = ids[__ffs((int) side[e]) - 1];
+              else { kid[e] = ids[TL_LEAVES + next++]; L.stack[sp][0] = side[e]; L.stack[sp][1] = kid[e]; sp++; }
+              T.parent[kid[e]] = id;
+            }
+            T.left[id] = kid[0]; T.right[id] = kid[1];
+            if (id != root) {
+              const int first = __ffs((int) s) - 1;
+              Box6 b = L.box[first];
+              uint32_t m = L.cnt[first];
+              for (int j = first + 1; j < TL_LEAVES; j++)
+                if (s >> j & 1) { b = box_union(b, L.box[j]); m += L.cnt[j]; }
+              T.box[id] = b; T.count[id] = m;
+              C[id - (uint32_t) n] = L.copt[s];
+            }
+          }
+          C[root - (uint32_t) n] = L.copt[TL_SETS - 1];
+          n_changed++;
+        }
+      }
+    }
+    if (active) {
+      p = T.parent[p];
+      if (p == NO_NODE) active = false;
+    }
+  }
+  if (n_changed) atomicAdd(changed, (unsigned long long) n_changed);
+}
+
+// the cost of the whole tree in f64 (what the scene reports): the same model bottom-up, k_fit's walk
+__device__ __forceinline__ double half_area64(const Box6 &b)
+{
+  const double dx = (double) b.mx[0] - (double) b.mn[0], dy = (double) b.mx[1] - (double) b.mn[1], dz = (double) b.mx[2] - (double) b.mn[2];
+  return dx * dy + dy * dz + dz * dx;
+}
+
+__global__ void __launch_bounds__(LB) k_sah_cost(int n, BTree T, double *C64, double trav)
+{
+  const int i = blockIdx.x * LB + threadIdx.x;
+  if (i >= n) return;
+  uint32_t p = T.parent[i];
+  while (p != NO_NODE) {
+    __threadfence();
+    if (atomicAdd(&T.flag[p - (uint32_t) n], 1) == 0) return;
+    __threadfence();
+    const uint32_t l = T.left[p], r = T.right[p], cnt = T.count[p];
+    const double cl = l < (uint32_t) n ? half_area64(T.box[l]) : C64[l - (uint32_t) n];
+    const double cr = r < (uint32_t) n ? half_area64(T.box[r]) : C64[r - (uint32_t) n];
+    const double a = half_area64(T.box[p]);
+    double c = trav * a + (cl + cr);
+    if (cnt <= (uint32_t) FJ_MAX_LEAF_PRIMS) c = fmin(c, a * (double) cnt);
+    C64[p - (uint32_t) n] = c;
+    p = T.parent[p];
+  }
+}
+
 // ---- collapse to 4-wide nodes, top-down one level per launch; the triangles of the subtree
 // under a queue entry take the slots [first, first + count) of the final order, so a subtree
 // of <= FJ_MAX_LEAF_PRIMS leaves is one leaf of the wide tree with contiguous triangles
@@ -353,7 +576,7 @@ template <class T> hipError_t dalloc(T **p, size_t n) { return hipMalloc((void *
 #define LB_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { *err = std::string("device BLAS build: ") + #expr + ": " + hipGetErrorString(e_); goto fail; } } while (0)
 
 int LbvhBuildMesh(const double *d_P, const double *d_vel, const int32_t *d_idx, int n_faces, int n_points,
-    const double bounds[6], bool f32_exact, int quality, LbvhOut *out, std::string *err)
+    const double bounds[6], bool f32_exact, int quality, int treelet_passes, LbvhOut *out, std::string *err)
 {
   const int n = n_faces;
   std::memset(out, 0, sizeof(*out));
@@ -369,6 +592,9 @@ int LbvhBuildMesh(const double *d_P, const double *d_vel, const int32_t *d_idx, 
   DNode *wide = nullptr;
   uint32_t *order = nullptr;
   int *bad = nullptr;
+  float *cost32 = nullptr;                       // [n] treelet passes: C of the inner nodes
+  double *cost64 = nullptr;                      // [n] the reported cost
+  unsigned long long *changed = nullptr;
   const unsigned grid = (unsigned) ((n + LB - 1) / LB);
   int levels = 0;
   uint32_t root2 = 0;
@@ -498,6 +724,48 @@ int LbvhBuildMesh(const double *d_P, const double *d_vel, const int32_t *d_idx, 
     if (getenv("FJGPU_VERBOSE") && n > 100000) fprintf(stderr, "fjgpu: clustering build: %d rounds, window radius %d\n", rounds, radius);
   }
 
+  // SAH cost of the tree as formed, treelet passes (off unless asked for: the tree below is then today's), cost afterwards
+  {
+    if (!T.parent) LB_TRY(dalloc(&T.parent, (size_t) 2 * n));
+    if (!T.flag) LB_TRY(dalloc(&T.flag, (size_t) n));
+    LB_TRY(dalloc(&cost64, (size_t) n)); LB_TRY(dalloc(&changed, 1));
+    hipLaunchKernelGGL(k_parents, dim3(grid), dim3(LB), 0, 0, n, root2, T);
+    auto tree_cost = [&](double *value) -> hipError_t {
+      hipError_t e = hipMemset(T.flag, 0, sizeof(int) * (size_t) n);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_sah_cost, dim3(grid), dim3(LB), 0, 0, n, T, cost64, (double) trav_cost);
+      double c = 0.;
+      Box6 rb;
+      if ((e = hipMemcpy(&c, cost64 + (root2 - (uint32_t) n), sizeof(c), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+      if ((e = hipMemcpy(&rb, T.box + root2, sizeof(rb), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+      const double dx = (double) rb.mx[0] - (double) rb.mn[0], dy = (double) rb.mx[1] - (double) rb.mn[1], dz = (double) rb.mx[2] - (double) rb.mn[2];
+      const double a = dx * dy + dy * dz + dz * dx;
+      *value = a > 0. ? c / a : 0.;
+      return hipSuccess;
+    };
+    LB_TRY(tree_cost(&out->sah_cost_initial));
+    out->sah_cost = out->sah_cost_initial;
+    if (treelet_passes > 0) {
+      const auto t0 = std::chrono::steady_clock::now();
+      LB_TRY(dalloc(&cost32, (size_t) n));
+      for (int pass = 0; pass < treelet_passes; pass++) {
+        LB_TRY(hipMemset(T.flag, 0, sizeof(int) * (size_t) n));
+        LB_TRY(hipMemset(changed, 0, sizeof(*changed)));
+        hipLaunchKernelGGL(k_treelet_pass, dim3(grid), dim3(LB), 0, 0, n, T, cost32, trav_cost, changed);
+        unsigned long long hc = 0;
+        LB_TRY(hipMemcpy(&hc, changed, sizeof(hc), hipMemcpyDeviceToHost));
+        out->treelet_passes++;
+        out->treelets_changed += hc;
+        if (hc == 0) break;                        // (a pass that rewrites nothing leaves the next one nothing to find)
+      }
+      const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (out->treelets_changed) LB_TRY(tree_cost(&out->sah_cost));
+      if (getenv("FJGPU_VERBOSE") && n > 100000)
+        fprintf(stderr, "fjgpu: treelet restructuring: %d passes in %.1f ms, %llu treelets rewritten, SAH cost %.4f -> %.4f\n",
+            out->treelet_passes, 1e3 * dt, out->treelets_changed, out->sah_cost_initial, out->sah_cost);
+    }
+  }
+
   // collapse, level by level from the root
   LB_TRY(dalloc(&qa, (size_t) n)); LB_TRY(dalloc(&qb, (size_t) n)); LB_TRY(dalloc(&counters, 2));
   LB_TRY(dalloc(&wide, (size_t) n)); LB_TRY(dalloc(&order, (size_t) n));
@@ -530,14 +798,16 @@ int LbvhBuildMesh(const double *d_P, const double *d_vel, const int32_t *d_idx, 
   out->stack_need = 3 * levels + 1;      // <= 3 siblings pushed per level
   for (void *p : {(void *) boxes, (void *) keys, (void *) keys2, (void *) vals, (void *) vals2, tmp, scan_tmp, (void *) T.left, (void *) T.right,
                   (void *) T.count, (void *) T.box, (void *) T.parent, (void *) T.flag, (void *) c0, (void *) c1, (void *) nn, (void *) marks,
-                  (void *) sums, (void *) total, (void *) qa, (void *) qb, (void *) counters, (void *) wide, (void *) bad})
+                  (void *) sums, (void *) total, (void *) qa, (void *) qb, (void *) counters, (void *) wide, (void *) bad, (void *) cost32, (void *) cost64,
+                  (void *) changed})
     if (p) (void) hipFree(p);
   return 0;
 
 fail:
   for (void *p : {(void *) boxes, (void *) keys, (void *) keys2, (void *) vals, (void *) vals2, tmp, scan_tmp, (void *) T.left, (void *) T.right,
                   (void *) T.count, (void *) T.box, (void *) T.parent, (void *) T.flag, (void *) c0, (void *) c1, (void *) nn, (void *) marks,
-                  (void *) sums, (void *) total, (void *) qa, (void *) qb, (void *) counters, (void *) wide, (void *) order, (void *) bad,
+                  (void *) sums, (void *) total, (void *) qa, (void *) qb, (void *) counters, (void *) wide, (void *) order, (void *) bad, (void *) cost32,
+                  (void *) cost64, (void *) changed,
                   (void *) out->nodes, (void *) out->prim_ids, (void *) out->tri_verts, (void *) out->tri_verts32, (void *) out->tri_vel})
     if (p) (void) hipFree(p);
   std::memset(out, 0, sizeof(*out));

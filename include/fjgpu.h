@@ -156,6 +156,10 @@ int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value);
  * build; 1: build the BLAS of meshes on the GPU by locally-ordered clustering (surface-area agglomeration over the
  * Morton order); 2: on the GPU as the radix tree of the Morton codes (fastest build, slowest tree); -1 (default): not
  * set -- the host build, or, for scenes created while "single_frame_build" is 1, the GPU's clustering build.
+ * "blas_treelet_passes" 0..8 (default 0): scenes created from now on run that many passes of SAH treelet restructuring (7-leaf treelets,
+ * the cheapest of all trees over them by dynamic programming; Karras & Aila 2013) over a GPU-built BLAS -- either builder -- before its collapse
+ * to 4-wide nodes; a pass that rewrites nothing is the last.  0: the tree as the builder formed it.  The host build ignores it.  The environment
+ * variable FJGPU_TREELET_PASSES, read at scene creation, wins over the option.  Closest hits do not depend on it; node counts and counters do.
  * "multi_exchange" 0/1: how fjgpu_render_frame_multi moves the devices' tile slabs to the first device -- 0 (default): one hipMemcpyPeer per
  * device (over xGMI where peer access exists; nothing to bring up, which is what a one-frame process wants); 1: RCCL -- once EVERY device has
  * rendered and packed its share, one ncclGroupStart / ncclGroupEnd holds each device's ncclSend and the first device's ncclRecv for it (the
@@ -210,7 +214,10 @@ int fjgpu_host_instance_level(const fj_scene_desc *desc, int group, int32_t *out
 /* Facts about the built device scene (for measurement: record sizes of the actual layout).
  * "node_record_bytes" (128; "anyhit_node_record_bytes" 64: the lean any-hit walk reads the quantised
  * twin of a node), "tri_record_bytes" (36 when every mesh is stored as exact f32
- * triangles, else 72), "blas_nodes", "stack_need", "lean_anyhit" (1: shadow rays are walked by
+ * triangles, else 72), "blas_nodes", "stack_need", "blas_treelet_passes" / "blas_treelets_changed" (treelet passes actually run / treelets
+ * rewritten in them), "blas_sah_cost_initial" / "blas_sah_cost" (SAH cost of the binary tree over its root's half area -- the leaf rule's model:
+ * C(triangle) = A, C(inner) = min(trav A + C(l) + C(r), A count for count <= 4) -- as the builder formed it / after the passes; equal with 0
+ * passes; all four are sums over the scene's GPU-built meshes and 0 when there is none), "lean_anyhit" (1: shadow rays are walked by
  * k_shadow_anyhit, 0: not), "curve_anyhit" (1: by k_shadow_anyhit_curves -- curve scene, every occluder opaque, no motion; both 0: by the
  * general k_shadow_trace), "closest_kernel" (0 k_trace_closest, 1 k_trace_closest_phased,
  * 2 its curve instantiation, 3 its motion instantiation, 4 k_trace_closest_flat: one world-space tree per group), "closest_node_record_bytes" (64: the closest-hit walk reads the
