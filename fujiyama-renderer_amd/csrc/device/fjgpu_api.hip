@@ -155,7 +155,8 @@ struct fjgpu_scene {
   long batch_samples = 0;          // option "batch_samples": samples per batch where batch_tiles is 0 (0: as many as the memory budget holds)
   long render_calls = 0;           // fjgpu_render_tiles calls that rendered something (the first one sizes its batches for a cold start)
   long count_events;
-  long count_all_shadow;
+  long count_all_shadow;           // option "count_all_shadow" (default 1): light records of weight zero reach the light loop, which counts their shadow rays as the
+                                   // reference does; it never queues them (their colour is exactly zero), so nothing walks them.  0: k_shade drops such records (other counts)
   // queries "stack_peak" / "stack_peak_closest" / "stack_peak_shadow": the most entries any lane's traversal stack held in the launches of the
   // last render_* / trace call (counting instantiations only, option count_nodes; 0 without it)
   unsigned long long stack_peak_closest = 0, stack_peak_shadow = 0;

@@ -12,7 +12,8 @@
 // against the world AABBs of the shadow group's instances: if it misses all of them
 // the light is unoccluded and Kd * Cl goes into the lane's per-record sum (W * sum is
 // added to the sample at the end); otherwise the ray is appended -- ballot + prefix
-// count into a chunk the wave reserved -- to the compact shadow-ray queue.
+// count into a chunk the wave reserved -- to the compact shadow-ray queue.  A pair
+// whose colour W * k is exactly zero is counted and neither tested nor queued.
 //
 // k_shadow_trace: the compact queue only, so every lane of a wave is
 // traversing (no lanes idling while a neighbour walks the BLAS).  Adds
@@ -124,6 +125,9 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
     const bool active = (r0 + lane) < slice_end;
 
     float sum[3] = {0.f, 0.f, 0.f};
+    // the record's own events, added to the lane's 64-bit totals after its lights (the totals, stepped inside the light loop, cost a second
+    // register pair each for the lanes that skip a step; one record's lights x instances stay far below 2^32)
+    uint32_t r_insts = 0, r_shadow = 0;
     uint32_t r_sample = 0;
     float W[3] = {0.f, 0.f, 0.f};
     const uint32_t nl = (uint32_t) S.n_light_samples;
@@ -134,12 +138,11 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
     R.uid = R.key = 0; R.kind = 0;
     XS xs = {0, 0, 0, 0};
     V3 Ps = mk(0, 0, 0), axis = Ps, nml_axis = Ps;
-    int g_first = 0, g_count = 0;
+    int g_first = 0, g_count = 0;          // the group's nodes; of a single-instance group g_first is its INSTANCE (its one node is not read again)
     bool g_single = false;
-    int g_inst = 0;                        // the instance of a single-instance group
     const double *g_sbounds = nullptr;     // stays a global-memory pointer (a by-value DGroup lands in scratch)
     double sb[6] = {0, 0, 0, 0, 0, 0};
-    double cos_limit = 0;
+    double cos_limit = kHair ? 0 : sp.cos_half_pi;     // (without hair the limit is the same for every lane: a scalar, not a register pair per lane)
     if (active) {
       R = lrecs[rec];
       if (kHair && (R.kind & 1)) H = S.lrec_hair[rec];
@@ -148,13 +151,13 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
       nml_axis = normalize(axis);
       r_sample = R.sample;
       W[0] = R.W[0]; W[1] = R.W[1]; W[2] = R.W[2];
-      cos_limit = (!kHair || (R.kind & 1) == 0) ? sp.cos_half_pi : sp.cos_pi;
+      if (kHair) cos_limit = (R.kind & 1) == 0 ? sp.cos_half_pi : sp.cos_pi;
       g_first = S.groups[R.group].first; g_count = S.groups[R.group].count;
       g_single = S.groups[R.group].n_instances == 1;
       g_sbounds = S.groups[R.group].sbounds;
       // a single-instance group's box is the same for every light of the record: read it once
       // (per pair it cost two dependent loads -- node, then box -- before any arithmetic)
-      if (g_single) { for (int q = 0; q < 6; q++) sb[q] = g_sbounds[q]; g_inst = gnodes[g_first].inst; }
+      if (g_single) { for (int q = 0; q < 6; q++) sb[q] = g_sbounds[q]; g_first = gnodes[g_first].inst; }
     }
     // A surface point well inside that box (every point of the occluder itself, but for its outermost
     // 2e-4) needs no box test per light: the unit-length ray leaves the box at t >= 2e-4 > tmin and
@@ -264,17 +267,25 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
             k[1] = (H.Cd[1] * diff + spec) * Cl[1];
             k[2] = (H.Cd[2] * diff + spec) * Cl[2];
           }
+          // A pair whose contribution W * k (the three floats that would be the queue entry's colour) is exactly zero is
+          // counted as a shadow ray where the reference counts it and goes no further: whatever a walk finds, it adds
+          // nothing.  The test is `== 0.f` on the PRODUCTS, not on W: -0.f is a zero, a NaN product (0 * inf, a NaN
+          // weight) is not, so it keeps the old path and poisons the sample as before.  Nothing goes into `sum` either:
+          // W * sum of such terms is zero too, except where non-zero W times non-zero k underflows while the pair also
+          // missed every box -- below 1e-38 absolute.  (C3: the mirror dragon's records, diffuse 0 -> W = 0.)
+          const bool carries = !(W[0] * k[0] == 0.f && W[1] * k[1] == 0.f && W[2] * k[2] == 0.f);
           bool maybe_occluded = false;
           if (sp.cast_shadow) {
-            c_shadow++;
+            r_shadow++;
             // group bounds test + leaf bounds of the instance BVH, as culling
-            if (deep_inside) maybe_occluded = !has_negative_zero(Ln);
-            else if (!has_negative_zero(Ln)) {
+            const bool test = carries && !has_negative_zero(Ln);
+            if (deep_inside) maybe_occluded = test;
+            else if (test) {
               const V3 winv = mk(filter_rcp(Ln.x), filter_rcp(Ln.y), filter_rcp(Ln.z));
               const bool plain = plain_dir(Ln);
               if (g_single) {
                 maybe_occluded = box_ray_ref_fast(sb, Ps, Ln, winv, plain, .0001, distance);
-                if (!maybe_occluded) c_insts++;
+                if (!maybe_occluded) r_insts++;
               }
               if (kSplit && !g_single && sp.join_capacity) {
                 pending = true; tcur = g_first; winv_s = winv; plain_s = plain; Ln_s = Ln; dist_s = distance;
@@ -289,7 +300,7 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
                 }
                 ti++;
                 if (box_ray_ref_fast(tn_->box, Ps, Ln, winv, plain, .0001, distance)) { maybe_occluded = true; break; }
-                c_insts++;
+                r_insts++;
               }
             }
           }
@@ -301,8 +312,8 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
             q.c[0] = W[0] * k[0]; q.c[1] = W[1] * k[1]; q.c[2] = W[2] * k[2];
             // (lean any-hit walk: a single-instance group's only candidate is settled here)
             // (tindex: the sample's slot in the time table for the general walk; in split mode the join slot, 0 = none)
-            q.sample = r_sample; q.group = (sp.pre_resolve && g_single) ? ~g_inst : R.group; q.tindex = (kSplit && sp.join_capacity) ? 0u : ((uint32_t) R.kind >> 1);
-          } else if (!kSplit || !pending) {
+            q.sample = r_sample; q.group = (sp.pre_resolve && g_single) ? ~g_first : R.group; q.tindex = (kSplit && sp.join_capacity) ? 0u : ((uint32_t) R.kind >> 1);
+          } else if (carries && (!kSplit || !pending)) {
             sum[0] += k[0]; sum[1] += k[1]; sum[2] += k[2];
           }
         }
@@ -324,7 +335,7 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
           if (box_ray_ref_fast(tn_->box, Ps, Ln_s, winv_s, plain_s, .0001, dist_s)) {
             if (nb == 0u) cb0 = tn_->inst; else if (nb == 1u) cb1 = tn_->inst; else if (nb == 2u) cb2 = tn_->inst; else cb3 = tn_->inst;
             nb++;
-          } else c_insts++;
+          } else r_insts++;
         }
         if (nb == 0u) {
           pending = false;
@@ -396,6 +407,7 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
       }
       if (kSplit && ncand >= 2) S.shadow_join[jslot1 - 1u] = ncand << 16;
     }
+    c_insts += r_insts; c_shadow += r_shadow;
     if (active) {
       float *acc = s_accum + 4 * (size_t) r_sample;
       const float r0v = W[0] * sum[0], r1v = W[1] * sum[1], r2v = W[2] * sum[2];

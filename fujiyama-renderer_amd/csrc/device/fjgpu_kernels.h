@@ -31,7 +31,8 @@ struct AdaptiveParams {       // AdaptiveGridSampler, src/fj_adaptive_grid_sampl
 
 struct ShadeParams {
   int32_t max_diffuse_depth, max_reflect_depth, max_refract_depth;
-  int32_t count_all_shadow;    // 1: trace zero-weight light records too (reference ray counts)
+  int32_t count_all_shadow;    // 1: zero-weight light records go to the light loop too, so that their shadow rays are COUNTED (reference ray counts);
+                               // they are never queued or traced (k_shadow_cull: a pair whose colour is exactly zero)
   uint32_t ray_capacity, light_capacity;
   // ray-queue sort (fjgpu_raysort.hip): the key of a child ray is computed where the ray is emitted -- origin and direction
   // are in registers there -- instead of by a pass of its own over the queue (C4: 1.6 G rays x 48 B less read per frame)
