@@ -153,6 +153,7 @@ struct fjgpu_scene {
   // options
   long batch_tiles;
   long batch_samples = 0;          // option "batch_samples": samples per batch where batch_tiles is 0 (0: as many as the memory budget holds)
+  long aov_batch_samples = 0;      // option "aov_batch_samples": samples per batch of fjgpu_render_aov (0: FJ_AOV_BATCH_SAMPLES)
   long render_calls = 0;           // fjgpu_render_tiles calls that rendered something (the first one sizes its batches for a cold start)
   long count_events;
   long count_all_shadow;           // option "count_all_shadow" (default 1): light records of weight zero reach the light loop, which counts their shadow rays as the
@@ -1115,6 +1116,7 @@ int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value)
   const std::string n(name);
   if (n == "batch_tiles") { scene->batch_tiles = value; return 0; }
   if (n == "batch_samples") { scene->batch_samples = value < 0 ? 0 : value; return 0; }
+  if (n == "aov_batch_samples") { scene->aov_batch_samples = value < 0 ? 0 : value; return 0; }
   if (n == "count_nodes") { scene->count_events = value != 0; return 0; }
   if (n == "count_all_shadow") { scene->count_all_shadow = value != 0; return 0; }
   if (n == "overlap_shadow") {
@@ -2040,6 +2042,205 @@ int fjgpu_trace(fjgpu_scene *sc, int group, int n, const double *rays, double *o
     stats->trace_ms = ms; stats->total_ms = ms; stats->trace_launches = 1;
   }
   return 0;
+}
+
+// ---- first-hit AOV pass.  Shaped like fjgpu_trace, not like the wavefront loop: transient buffers per call, nothing of the scene's work arena,
+// options or call counters is touched, so the beauty renders around it see the scene they saw before.
+#ifndef FJ_AOV_BATCH_SAMPLES
+#define FJ_AOV_BATCH_SAMPLES ((long) 4 << 20)      // 132 bytes per sample: uv, ray, path and hit records of half a GB per batch
+#endif
+
+// what fjgpu_render_aov and fjgpu_camera_samples share: the refusals, the tiling, the sampler's parameters, the per-call DScene
+struct AovSetup {
+  std::vector<fjgpu::TileRect> all;
+  int margin[2];
+  GenParams gp;
+  DScene S;
+};
+static int aov_setup(fjgpu_scene *sc, const fj_render_desc *r, const char *who, AovSetup *a)
+{
+  if (r->sampler_type == 1) return fail(FJGPU_EUNSUPPORTED, std::string(who) + ": the adaptive sampler is not supported (fixed-grid sampler only)");
+  if (r->sampler_type != 0) return fail(FJGPU_EINVAL, "unknown sampler_type");
+  if (const char *why = bad_render(r)) return fail(FJGPU_EINVAL, why);
+  if (sc->S.cam_xform) return fail(FJGPU_EUNSUPPORTED, std::string(who) + ": a time-sampled camera is not supported (static cameras only)");
+  if (sc->S.has_motion) return fail(FJGPU_EUNSUPPORTED, std::string(who) + ": a scene with motion (time-sampled transforms or vertex velocities) is not supported (static scenes only)");
+  fjgpu::GenerateTiles(*r, &a->all);
+  fjgpu::SamplerMargin(*r, a->margin);
+  GenParams &gp = a->gp;
+  gp.rate_x = r->rate_x; gp.rate_y = r->rate_y; gp.margin_x = a->margin[0]; gp.margin_y = a->margin[1];
+  gp.udelta = 1. / (r->rate_x * r->xres);
+  gp.vdelta = 1. / (r->rate_y * r->yres);
+  gp.jitter = r->jitter;
+  gp.jittered = r->jitter > 0 ? 1 : 0;
+  gp.pad = 0;
+  // camera (Renderer::preprocess_camera + Camera::compute_uv_size), as render_tiles_once sets it
+  a->S = sc->S;
+  const double aspect = r->xres / (double) r->yres;
+  a->S.cam_uv_size[1] = fjgpu::CameraUvSizeY(sc->cam_fov);
+  a->S.cam_uv_size[0] = a->S.cam_uv_size[1] * aspect;
+  a->S.time_start = r->time_start; a->S.time_end = r->time_end;
+  a->S.lrec_hair = nullptr;
+  a->S.cam_uv = nullptr; a->S.cam_tk = nullptr; a->S.cam_slot0 = 0;
+  a->S.trace_ranges = nullptr; a->S.trace_n_dev = nullptr; a->S.ray_perm = nullptr;
+  a->S.shadow_join = nullptr;
+  return 0;
+}
+static TileDesc aov_tile(const fj_render_desc *r, const fjgpu::TileRect &t, const int *margin, uint32_t sample_offset)
+{
+  TileDesc d;
+  d.xmin = t.xmin; d.ymin = t.ymin; d.xmax = t.xmax; d.ymax = t.ymax; d.id = t.id;
+  d.nx = r->rate_x * (t.xmax - t.xmin) + 2 * margin[0];
+  d.ny = r->rate_y * (t.ymax - t.ymin) + 2 * margin[1];
+  d.sample_offset = sample_offset; d.cell_offset = 0; d.pad = 0;
+  return d;
+}
+
+int fjgpu_render_aov(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
+    const fjgpu_aov_buffers *out, void *hip_stream, fjgpu_stats *stats)
+{
+  if (!sc || !r || !out) return fail(FJGPU_EINVAL, "fjgpu_render_aov: null argument");
+  if (!out->depth && !out->position && !out->normal && !out->uv && !out->ids && !out->coverage)
+    return fail(FJGPU_EINVAL, "fjgpu_render_aov: every buffer pointer is NULL, nothing to write");
+  if (tile_ids && n_tiles < 0) return fail(FJGPU_EINVAL, "fjgpu_render_aov: negative tile count");
+  AovSetup A;
+  if (const int e = aov_setup(sc, r, "fjgpu_render_aov", &A)) return e;
+  HIP_TRY(hipSetDevice(sc->device));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+
+  std::vector<int> ids;
+  if (tile_ids) ids.assign(tile_ids, tile_ids + n_tiles);
+  else for (size_t i = 0; i < A.all.size(); i++) ids.push_back((int) i);
+  for (int id : ids) if (id < 0 || id >= (int) A.all.size()) return fail(FJGPU_EINVAL, "tile id out of range");
+  fjgpu_stats acc;
+  std::memset(&acc, 0, sizeof(acc));
+  if (ids.empty()) { if (stats) *stats = acc; return 0; }
+
+  // batches: tiles in list order, at most `limit` samples each (a batch holds at least one tile; the tile index is grid.y: at most 65535)
+  const size_t limit = (size_t) std::min<long>(sc->aov_batch_samples > 0 ? sc->aov_batch_samples : FJ_AOV_BATCH_SAMPLES, 0x7fffffffL);
+  struct Batch { size_t first; int n; uint32_t samples, max_ts; int max_px; };
+  std::vector<TileDesc> td(ids.size());
+  std::vector<Batch> batches;
+  size_t cap_samples = 0, tab_len = 0;
+  for (size_t k = 0; k < ids.size(); k++) {
+    const fjgpu::TileRect &t = A.all[ids[k]];
+    TileDesc d = aov_tile(r, t, A.margin, 0);
+    const size_t ts = (size_t) d.nx * (size_t) d.ny;
+    if (ts > 0x7fffffffu) return fail(FJGPU_EINVAL, "fjgpu_render_aov: a tile of more than 2^31 samples: lower the tilesize");
+    if (batches.empty() || batches.back().n >= 65535 || (size_t) batches.back().samples + ts > limit) batches.push_back(Batch{k, 0, 0u, 0u, 0});
+    Batch &b = batches.back();
+    d.sample_offset = b.samples;
+    td[k] = d;
+    b.n++; b.samples += (uint32_t) ts;
+    b.max_ts = std::max(b.max_ts, (uint32_t) ts);
+    b.max_px = std::max(b.max_px, (t.xmax - t.xmin) * (t.ymax - t.ymin));
+    cap_samples = std::max(cap_samples, (size_t) b.samples);
+    tab_len = std::max(tab_len, ts);
+  }
+
+  DeviceBuffers W;
+  double *d_suv; DRay *d_rays; DPath *d_paths; DHit *d_hits; DCounters *d_cnt; TileDesc *d_tiles;
+  const double *d_jit = nullptr;
+  if (W.alloc(cap_samples * 2, &d_suv) || W.alloc(cap_samples, &d_rays) || W.alloc(cap_samples, &d_paths) || W.alloc(cap_samples, &d_hits) ||
+      W.alloc(1, &d_cnt) || W.alloc(td.size(), &d_tiles))
+    return fail(FJGPU_ENOMEM, "fjgpu_render_aov: device allocation failed: lower the aov_batch_samples option");
+  {
+    // the per-tile XorShift stream as a table (draw k is the same number in every tile): two draws per sample of the largest tile
+    std::vector<double> draws;
+    fjgpu::XorShiftTable(2 * tab_len, &draws);
+    if (W.upload(draws.data(), 2 * tab_len, &d_jit)) return fail(FJGPU_ENOMEM, "fjgpu_render_aov: device allocation failed");
+  }
+  HIP_TRY(hipMemcpy(d_tiles, td.data(), sizeof(TileDesc) * td.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_cnt, 0, sizeof(DCounters)));
+  DScene S = A.S;
+  S.time_tab = d_jit;      // (never read: no motion, a static camera)
+  AovParams ap;
+  ap.xres = r->xres; ap.rate_x = r->rate_x; ap.rate_y = r->rate_y; ap.margin_x = A.margin[0]; ap.margin_y = A.margin[1]; ap.pad = 0;
+  ap.depth = out->depth; ap.position = out->position; ap.normal = out->normal; ap.uv = out->uv; ap.ids = out->ids; ap.coverage = out->coverage;
+
+  // event pairs around every launch, turned into durations after the one synchronisation at the end
+  struct Span { hipEvent_t a, b; double *bucket; };
+  std::vector<Span> spans;
+  hipEvent_t ev_all[2] = {nullptr, nullptr};
+  auto drop_events = [&]() {
+    for (Span &sp : spans) { (void) hipEventDestroy(sp.a); (void) hipEventDestroy(sp.b); }
+    for (hipEvent_t e : ev_all) if (e) (void) hipEventDestroy(e);
+  };
+  auto timed = [&](double *bucket, auto &&launch) -> int {
+    Span sp{nullptr, nullptr, bucket};
+    if (hipEventCreate(&sp.a) != hipSuccess) return -1;
+    if (hipEventCreate(&sp.b) != hipSuccess) { (void) hipEventDestroy(sp.a); return -1; }
+    spans.push_back(sp);
+    (void) hipEventRecord(sp.a, st);
+    const int le = launch();
+    (void) hipEventRecord(sp.b, st);
+    return le;
+  };
+  int rc = 0;
+  if (hipEventCreate(&ev_all[0]) != hipSuccess || hipEventCreate(&ev_all[1]) != hipSuccess) rc = -1;
+  if (!rc) (void) hipEventRecord(ev_all[0], st);
+  for (size_t b = 0; b < batches.size() && rc == 0; b++) {
+    const Batch &B = batches[b];
+    const TileDesc *tiles = d_tiles + B.first;
+    rc = timed(&acc.gen_ms, [&]() { return launch_gen_camera(st, S, A.gp, tiles, B.n, B.max_ts, d_jit, d_jit, d_suv, d_rays, d_paths); });
+    if (rc) break;
+    rc = timed(&acc.closest_ms, [&]() { return launch_trace_closest(st, S, d_rays, d_paths, d_hits, B.samples, d_cnt, (int) sc->count_events); });
+    if (rc) break;
+    rc = timed(&acc.resolve_ms, [&]() { return launch_aov_reduce(st, S, ap, tiles, B.n, B.max_px, d_rays, d_hits); });
+    if (rc) break;
+    acc.rays.camera += B.samples;
+    acc.trace_launches++; acc.closest_launches++; acc.batches++;
+  }
+  if (ev_all[1]) (void) hipEventRecord(ev_all[1], st);
+  const hipError_t se = hipStreamSynchronize(st);      // (also before the transient buffers go away)
+  if (rc == 0 && se == hipSuccess) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev_all[0], ev_all[1]) == hipSuccess) acc.total_ms = ms;
+    for (const Span &sp : spans) if (hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) *sp.bucket += ms;
+    acc.trace_ms = acc.closest_ms;
+  }
+  drop_events();
+  if (rc) return fail(FJGPU_ENODEV, std::string("fjgpu_render_aov: HIP failure: ") + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
+  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string("fjgpu_render_aov: stream synchronize: ") + hipGetErrorString(se));
+  if (stats) {
+    DCounters hc;
+    HIP_TRY(hipMemcpy(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost));
+    acc.nodes_visited = hc.nodes; acc.prims_tested = hc.prims; acc.insts_tested = hc.insts; acc.rays_traced = hc.traced;
+    *stats = acc;
+  }
+  return 0;
+}
+
+int fjgpu_camera_samples(fjgpu_scene *sc, const fj_render_desc *r, int tile_id, double *rays8, int cap)
+{
+  if (!sc || !r || (!rays8 && cap > 0) || cap < 0) return fail(FJGPU_EINVAL, "fjgpu_camera_samples: null argument");
+  AovSetup A;
+  if (const int e = aov_setup(sc, r, "fjgpu_camera_samples", &A)) return e;
+  if (tile_id < 0 || tile_id >= (int) A.all.size()) return fail(FJGPU_EINVAL, "tile id out of range");
+  const TileDesc d = aov_tile(r, A.all[tile_id], A.margin, 0);
+  const size_t n = (size_t) d.nx * (size_t) d.ny;
+  if (n > 0x7fffffffu) return fail(FJGPU_EINVAL, "fjgpu_camera_samples: a tile of more than 2^31 samples");
+  if (cap == 0) return (int) n;
+  HIP_TRY(hipSetDevice(sc->device));
+  DeviceBuffers W;
+  double *d_suv; DRay *d_rays; DPath *d_paths;
+  const double *d_jit = nullptr; const TileDesc *d_tile = nullptr;
+  std::vector<double> draws;
+  fjgpu::XorShiftTable(2 * n, &draws);
+  if (W.alloc(n * 2, &d_suv) || W.alloc(n, &d_rays) || W.alloc(n, &d_paths) || W.upload(draws.data(), 2 * n, &d_jit) || W.upload(&d, 1, &d_tile))
+    return fail(FJGPU_ENOMEM, "fjgpu_camera_samples: device allocation failed");
+  DScene S = A.S;
+  S.time_tab = d_jit;
+  const int le = launch_gen_camera(nullptr, S, A.gp, d_tile, 1, (uint32_t) n, d_jit, d_jit, d_suv, d_rays, d_paths);
+  if (le) return fail(FJGPU_ENODEV, std::string("fjgpu_camera_samples: launch: ") + hipGetErrorString((hipError_t) le));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<DRay> h(n);
+  HIP_TRY(hipMemcpy(h.data(), d_rays, sizeof(DRay) * n, hipMemcpyDeviceToHost));
+  const size_t m = std::min(n, (size_t) cap);
+  for (size_t i = 0; i < m; i++) {
+    for (int k = 0; k < 3; k++) { rays8[8 * i + k] = h[i].o[k]; rays8[8 * i + 3 + k] = h[i].d[k]; }
+    rays8[8 * i + 6] = S.cam_znear; rays8[8 * i + 7] = S.cam_zfar;      // the range of a camera ray (Camera::GetRay, src/fj_camera.cc:105-106)
+  }
+  return (int) n;
 }
 
 }  // extern "C"

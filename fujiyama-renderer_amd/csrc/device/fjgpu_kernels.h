@@ -20,6 +20,13 @@ struct GenParams {
   int32_t jittered, pad;
 };
 
+struct AovParams {             // fjgpu_render_aov: the reduce kernel's view of the call (fjgpu_dev_aov.h)
+  int32_t xres, rate_x, rate_y, margin_x, margin_y, pad;
+  float *depth, *position, *normal, *uv;     // DEVICE buffers of the frame, row-major; null = not wanted (fjgpu_aov_buffers)
+  int32_t *ids;
+  float *coverage;
+};
+
 struct AdaptiveParams {       // AdaptiveGridSampler, src/fj_adaptive_grid_sampler.cc
   int32_t D, div;              // adaptive_max_subdivision, 2^D lattice cells per pixel
   int32_t margin_x, margin_y;  // filter margin in PIXELS: ceil(filterwidth - 1)
@@ -84,6 +91,10 @@ size_t persistent_threads();
 // sample values: f32 RGBA as accumulated (fixed grid) or f64 RGBA (adaptive grid: interpolated samples)
 int launch_resolve(hipStream_t st, const ResolveParams &rp, const TileDesc *d_tiles, int n_tiles, int max_tile_pixels,
     const double *s_uv, const float *s_accum, const double *s_data64, float *fb);
+
+// first-hit AOV pass (fjgpu_dev_aov.h): the own samples of every pixel of the batch's tiles reduced to the nearest hit, its attributes written out
+int launch_aov_reduce(hipStream_t st, const DScene &S, const AovParams &ap, const TileDesc *d_tiles, int n_tiles, int max_tile_pixels,
+    const DRay *rays, const DHit *hits);
 
 // adaptive grid sampler (fjgpu_dev_adaptive.h)
 int launch_adaptive_uv(hipStream_t st, const AdaptiveParams &ap, const TileDesc *d_tiles, int n_tiles, uint32_t max_tile_samples,

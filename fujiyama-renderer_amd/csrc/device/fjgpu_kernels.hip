@@ -14,6 +14,7 @@
 //   fjgpu_dev_shadow.h    k_shadow_cull (SlIlluminance light loop), k_shadow_trace
 //   fjgpu_dev_anyhit.h    k_shadow_anyhit (lean any-hit walk: phase-scheduled, f32 slabs)
 //   fjgpu_dev_anyhit_curves.h  k_shadow_anyhit_curves (the same scheduling for scenes with curve sets: + a ribbon phase)
+//   fjgpu_dev_aov.h       k_aov_reduce (fjgpu_render_aov: nearest own sample of every pixel, its hit attributes written out)
 //   fjgpu_dev_flat.h      k_trace_closest_flat (closest-hit walk of FLAT groups: one world-space culling tree per group, exact tests in object space)
 //   here                  k_resolve (reconstruct_image / apply_pixel_filter), host launchers
 #include <hip/hip_runtime.h>
@@ -39,6 +40,7 @@
 #include "fjgpu_dev_anyhit.h"
 #include "fjgpu_dev_anyhit_curves.h"
 #include "fjgpu_dev_adaptive.h"
+#include "fjgpu_dev_aov.h"
 
 // ------------------------------------------------------------------ k_resolve
 // reconstruct_image + apply_pixel_filter (src/fj_renderer.cc:939-995) with
@@ -517,6 +519,16 @@ int launch_resolve(hipStream_t st, const ResolveParams &rp, const TileDesc *d_ti
     hipLaunchKernelGGL(k_resolve<double4>, grid, dim3(BLOCK), 0, st, rp, d_tiles, s_uv, reinterpret_cast<const double4 *>(s_data64), fb);
   else
     hipLaunchKernelGGL(k_resolve<float4>, grid, dim3(BLOCK), 0, st, rp, d_tiles, s_uv, reinterpret_cast<const float4 *>(s_accum), fb);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_aov_reduce(hipStream_t st, const DScene &S, const AovParams &ap, const TileDesc *d_tiles, int n_tiles, int max_tile_pixels,
+    const DRay *rays, const DHit *hits)
+{
+  if (n_tiles <= 0 || max_tile_pixels <= 0) return 0;
+  const dim3 grid((max_tile_pixels + BLOCK / 64 - 1) / (BLOCK / 64), n_tiles);      // one wave per pixel
+  hipLaunchKernelGGL(k_aov_reduce, grid, dim3(BLOCK), 0, st, S, ap, d_tiles, rays, hits);
   LAUNCH_CHECK();
   return 0;
 }

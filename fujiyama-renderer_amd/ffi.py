@@ -54,6 +54,10 @@ class GpuStats(C.Structure):           # fjgpu_stats
     ]
 
 
+class AovBuffers(C.Structure):         # fjgpu_aov_buffers: DEVICE pointers, 0 = not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("depth", "position", "normal", "uv", "ids", "coverage")]
+
+
 class RenderStats(C.Structure):        # fj_render_stats
     _fields_ = [("render_seconds", C.c_double), ("prepare_seconds", C.c_double), ("rays", RayCounts)]
 

@@ -33,6 +33,9 @@ def lib():
                                                C.c_void_p, C.POINTER(ffi.GpuStats)]
         L.fjgpu_pack_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.fjgpu_unpack_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.fjgpu_render_aov.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_void_p, C.c_int, C.POINTER(ffi.AovBuffers),
+                                       C.c_void_p, C.POINTER(ffi.GpuStats)]
+        L.fjgpu_camera_samples.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_int, C.c_void_p, C.c_int]
         L.fjgpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.fjgpu_global_option.argtypes = [C.c_char_p, C.c_long]
         L.fjgpu_scene_query.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
@@ -51,11 +54,16 @@ def device_count():
     return lib().fjgpu_device_count()
 
 
+AOV_NAMES = ("depth", "position", "normal", "uv", "ids", "coverage")       # the members of fjgpu_aov_buffers
+AOV_CHANNELS = {"depth": 1, "position": 3, "normal": 3, "uv": 2, "ids": 4, "coverage": 1}
+
+
 class Scene(object):
     """Device-resident scene (BLAS, instances, lights, shaders, textures)."""
 
     def __init__(self, scene_desc_ptr, device=0):
         self._h = C.c_void_p()
+        self._device = device
         _check(lib().fjgpu_scene_create(scene_desc_ptr, device, C.byref(self._h)))
 
     def close(self):
@@ -107,6 +115,47 @@ class Scene(object):
         _check(lib().fjgpu_trace(self._h, group, n, rays.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
                                  ids.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p), C.byref(st)))
         return t, ids, uv, st
+
+    def render_aov(self, render, tile_ids=None, want=AOV_NAMES, prefill=None, stream=None):
+        """First-hit AOV pass (include/fjgpu.h: fjgpu_render_aov) of the listed tiles (None = all tiles of the render region):
+        the nearest of every pixel's own samples.  -> ({name: numpy array [H, W, channels]}, GpuStats) for the names in `want`:
+        depth [1] f32, position [3], normal [3], uv [2], ids [4] int32 (instance, primitive, shading group, shader index),
+        coverage [1].  The buffers are torch tensors on the scene's device; `prefill` (a number, or {name: number}) sets every
+        element beforehand, so that the pixels of tiles not listed can be told from those written (default 0)."""
+        import torch
+        want = tuple(want)
+        for name in want:
+            if name not in AOV_NAMES:
+                raise ValueError("unknown AOV %r (one of %s)" % (name, ", ".join(AOV_NAMES)))
+        dev = torch.device("cuda", self._device)
+        bufs = ffi.AovBuffers()
+        tensors = {}
+        for name in want:
+            dtype = torch.int32 if name == "ids" else torch.float32
+            fill = prefill.get(name, 0) if isinstance(prefill, dict) else (0 if prefill is None else prefill)
+            tensors[name] = torch.full((render.yres, render.xres, AOV_CHANNELS[name]), fill, dtype=dtype, device=dev)
+            setattr(bufs, name, tensors[name].data_ptr())
+        torch.cuda.synchronize(dev)          # the fills ran on torch's stream
+        st = ffi.GpuStats()
+        if tile_ids is None:
+            ids_p, n = None, 0
+        else:
+            ids = np.ascontiguousarray(tile_ids, dtype=np.int32)
+            ids_p, n = ids.ctypes.data_as(C.c_void_p), len(ids)
+        _check(lib().fjgpu_render_aov(self._h, C.byref(render), ids_p, n, C.byref(bufs), C.c_void_p(stream or 0), C.byref(st)))
+        return {name: t.cpu().numpy() for name, t in tensors.items()}, st
+
+    def camera_samples(self, render, tile_id):
+        """the camera rays of one tile as the AOV and beauty passes trace them (include/fjgpu.h: fjgpu_camera_samples) ->
+        ndarray [n, 8] = orig, dir, znear, zfar in sample order k = y * nx + x, margin samples included: what trace() takes"""
+        n = lib().fjgpu_camera_samples(self._h, C.byref(render), int(tile_id), None, 0)
+        if n < 0:
+            _check(n)
+        rays = np.empty((n, 8), dtype=np.float64)
+        m = lib().fjgpu_camera_samples(self._h, C.byref(render), int(tile_id), rays.ctypes.data_as(C.c_void_p), n)
+        if m < 0:
+            _check(m)
+        return rays
 
 
 class MultiScene(object):

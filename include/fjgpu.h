@@ -143,6 +143,56 @@ int fjgpu_unpack_tiles(float *d_fb, int xres, const int32_t *d_rects, int n_tile
 int fjgpu_trace(fjgpu_scene *scene, int group, int n, const double *rays,
     double *out_t, int32_t *out_ids, double *out_uv, fjgpu_stats *stats);
 
+/* First-hit AOV pass: the geometry behind every pixel -- depth for compositing, ids for mattes, position / normal / uv as
+ * feature buffers, what lies under a pixel for picking.  Static scenes with the fixed-grid sampler only.
+ *
+ * Tiles, tile ids, the render region and "pixels of tiles not listed are left untouched" are exactly those of
+ * fjgpu_render_tiles.  The samples are the beauty pass's own: a tile has nx * ny of them, rate * size + 2 * margin per axis
+ * (FixedGridSampler::generate_samples, src/fj_fixed_grid_sampler.cc:33-84), sample k = y * nx + x takes draw k of the jitter
+ * table and the same (u, v), and its camera ray is the static camera's (Camera::GetRay, src/fj_camera.cc:79-110).  ALL samples
+ * of a tile are traced, the filter margin included, so stats->rays.camera equals the beauty pass's camera count for those tiles.
+ * Only a pixel's OWN samples enter its reduction: for pixel (px, py) of a tile with corner (xmin, ymin) the rate_x * rate_y
+ * samples with x in [margin_x + (px - xmin) * rate_x, ... + rate_x) and y likewise.  The NEAREST sample is the own sample
+ * with the smallest t; on equal t the smallest k wins.  Its attributes are computed with the statements the shading kernel
+ * uses for a hit (trace_surface's SurfaceInput setup):
+ *   depth     (float) t
+ *   position  Pw = M (M^-1 o + t M^-1 d), the instance's matrices (ObjectInstance::RayIntersect, src/fj_object_instance.cc:213-243)
+ *   normal    normalize(M . ((1-u-v) n0 + u n1 + v n2)) from the mesh's per-corner normals where it has them, else its point
+ *             normals (compute_shading_normal, src/fj_mesh.cc:108-120); NOT face-forwarded; zero for a mesh without normals
+ *   uv        the f32 texture coordinates of Mesh::ray_intersect (src/fj_mesh.cc:285-290); zero for a mesh without them
+ *   ids       instance, primitive, shading group (the face's group, 0 without face groups), shader index by the slot rule of
+ *             ObjectInstance::GetShader (src/fj_object_instance.cc:177-191): a group out of range or an unassigned slot gives
+ *             slot 0; -1 only if slot 0 is unassigned
+ *   coverage  (float) hits / (float) samples among the pixel's own samples
+ * A hit on a curve writes normal and uv zero, as Curve::ray_intersect leaves them (src/fj_curve.cc:211-229), the curve's index
+ * in its set as the primitive and shading group 0.  A pixel none of whose own samples hits gets depth +INFINITY, ids -1 and
+ * zeros elsewhere.
+ *
+ * The call allocates its buffers per call and frees them before it returns; it touches neither the scene's work arena nor its
+ * options nor its call counters: beauty renders before and after it give the same pixels and counts.  The tile list is cut into
+ * batches of at most "aov_batch_samples" samples (fjgpu_set_option; default, and 0: 4 M; a batch holds at least one tile).
+ * Work is enqueued on `hip_stream` and the call returns after the stream has been synchronised.  stats (may be NULL):
+ * rays.camera, gen_ms (sample generation), closest_ms = trace_ms (the closest-hit walk), resolve_ms (the reduction),
+ * total_ms, batches, closest_launches; the traversal counters with option "count_nodes".
+ * Errors: FJGPU_EUNSUPPORTED, the reason named in the error string, for the adaptive sampler, for a time-sampled camera and
+ * for a scene with motion (query "has_motion"); FJGPU_EINVAL when every buffer pointer is NULL or an argument is NULL. */
+typedef struct fjgpu_aov_buffers {   /* DEVICE pointers, row-major xres*yres, NULL = not wanted */
+  float   *depth;      /* [1]  (float) t of the nearest sample, +INFINITY where no sample hits   */
+  float   *position;   /* [3]  world-space hit point                                             */
+  float   *normal;     /* [3]  interpolated shading normal in world space (not face-forwarded)   */
+  float   *uv;         /* [2]  texture coordinates of the hit                                    */
+  int32_t *ids;        /* [4]  instance, primitive, shading group (face group), shader index     */
+  float   *coverage;   /* [1]  hits / samples among the pixel's own samples                      */
+} fjgpu_aov_buffers;
+int fjgpu_render_aov(fjgpu_scene *scene, const fj_render_desc *render, const int32_t *tile_ids, int n_tiles,
+    const fjgpu_aov_buffers *buffers, void *hip_stream, fjgpu_stats *stats);
+
+/* Diagnostics: the camera rays of one tile exactly as fjgpu_render_aov (and the beauty pass) traces them, HOST arrays:
+ * rays8 [n][8] = orig xyz, dir xyz, znear, zfar in sample order k = y * nx + x (margin samples included) -- the layout
+ * fjgpu_trace takes.  Writes at most `cap` rays (cap 0: none, rays8 may be NULL); returns the tile's sample count n, or a
+ * negative error (the refusals of fjgpu_render_aov). */
+int fjgpu_camera_samples(fjgpu_scene *scene, const fj_render_desc *render, int tile_id, double *rays8, int cap);
+
 /* Tunables (all have defaults): "batch_tiles" tiles per wavefront batch, "batch_samples" samples per batch where batch_tiles is 0
  * (0, the default: as many as the memory budget holds -- fastest where frames repeat; a caller that renders one frame per scene
  * sets a few M: the work arena shrinks from ~110 GB to a few GB at the headline size and the cold frame starts sooner),
