@@ -21,6 +21,7 @@
 
 #include "fjgpu.h"
 #include "fjgpu_build.h"
+#include "fjgpu_denoise.h"
 #include "fjgpu_kernels.h"
 #include "fjgpu_lbvh.h"
 #include "fjgpu_raysort.h"
@@ -2207,6 +2208,78 @@ int fjgpu_render_aov(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *ti
     acc.nodes_visited = hc.nodes; acc.prims_tested = hc.prims; acc.insts_tested = hc.insts; acc.rays_traced = hc.traced;
     *stats = acc;
   }
+  return 0;
+}
+
+// ---- denoiser (fjgpu_denoise.hip, fjgpu_denoise_math.h).  Shaped like the AOV pass: no scene, transient buffers per call -- two RGBA frames
+// of the region for the iterations to ping-pong between and one 32-byte guide record per region pixel.  Iteration 0 reads color_in and the
+// last one writes color_out, every other end of an iteration is a scratch frame, so color_out may be color_in: with two or more iterations
+// no launch reads what it writes, and a single iteration in place filters a copy of the region.
+int fjgpu_denoise(int device, const fjgpu_denoise_desc *d, const float *color_in, const float *normal, const float *position,
+    const int32_t *ids, float *color_out, void *hip_stream, fjgpu_stats *stats)
+{
+  if (!d || !color_in || !color_out) return fail(FJGPU_EINVAL, "fjgpu_denoise: null argument (desc, color_in and color_out are required)");
+  if (d->xres <= 0 || d->yres <= 0) return fail(FJGPU_EINVAL, "fjgpu_denoise: resolution must be positive");
+  if (d->region[0] < 0 || d->region[1] < 0 || d->region[2] > d->xres || d->region[3] > d->yres ||
+      d->region[0] >= d->region[2] || d->region[1] >= d->region[3])
+    return fail(FJGPU_EINVAL, "fjgpu_denoise: region must be a non-empty rectangle inside the frame");
+  if (d->iterations < 1 || d->iterations > FJ_DN_MAX_ITERATIONS) return fail(FJGPU_EINVAL, "fjgpu_denoise: iterations must be 1..8");
+  if (std::isnan(d->sigma_color) || std::isnan(d->sigma_normal) || std::isnan(d->sigma_position))
+    return fail(FJGPU_EINVAL, "fjgpu_denoise: a sigma is NaN");
+  if (((uintptr_t) color_in | (uintptr_t) color_out) & 15u) return fail(FJGPU_EINVAL, "fjgpu_denoise: color_in and color_out must be 16-byte aligned");
+  const int w = d->region[2] - d->region[0], h = d->region[3] - d->region[1];
+  if (h > 65535 * 4) return fail(FJGPU_EINVAL, "fjgpu_denoise: a region of more than 262140 rows");
+  if (fjgpu_device_count() < 1) return fail(FJGPU_ENODEV, "fjgpu_denoise: no HIP device is visible");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const size_t npx = (size_t) w * (size_t) h;
+  const int n_it = d->iterations;
+  const int stop = (d->stop_at_ids && ids) ? 1 : 0;
+
+  DeviceBuffers W;
+  float *d_frame[2], *d_guide;
+  if (W.alloc(npx * 4, &d_frame[0]) || W.alloc(npx * 4, &d_frame[1]) || W.alloc(npx * 8, &d_guide))
+    return fail(FJGPU_ENOMEM, "fjgpu_denoise: device allocation failed");
+
+  fjgpu_stats acc;
+  std::memset(&acc, 0, sizeof(acc));
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};      // call start, guide pack done, iterations done
+  int rc = 0;
+  for (int k = 0; k < 3 && !rc; k++) if (hipEventCreate(&ev[k]) != hipSuccess) rc = -1;
+  const size_t origin = ((size_t) d->region[1] * (size_t) d->xres + (size_t) d->region[0]) * 4;
+  if (!rc) {
+    (void) hipEventRecord(ev[0], st);
+    rc = launch_dn_pack(st, normal, position, ids, d->xres, d->region[0], d->region[1], w, h, d_guide);
+    (void) hipEventRecord(ev[1], st);
+  }
+  const float *src = color_in + origin;
+  int src_stride = d->xres;
+  if (!rc && n_it == 1 && color_in == color_out) {
+    // in place with a single iteration: that launch would read pixels other blocks have written
+    if (hipMemcpy2DAsync(d_frame[1], (size_t) w * 16, src, (size_t) d->xres * 16, (size_t) w * 16, (size_t) h, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = -1;
+    src = d_frame[1]; src_stride = w;
+  }
+  for (int i = 0; i < n_it && !rc; i++) {
+    const bool last = i == n_it - 1;
+    float *dst = last ? color_out + origin : d_frame[i & 1];
+    const int dst_stride = last ? d->xres : w;
+    rc = launch_dn_atrous(st, src, src_stride, d_guide, dst, dst_stride, w, h, 1 << i, stop,
+                          fj_dn_constants(d->sigma_color, normal ? d->sigma_normal : 0.f, position ? d->sigma_position : 0.f, i));
+    src = dst; src_stride = dst_stride;
+  }
+  if (ev[2]) (void) hipEventRecord(ev[2], st);
+  const hipError_t se = hipStreamSynchronize(st);      // (also before the transient buffers go away)
+  if (rc == 0 && se == hipSuccess) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) acc.gen_ms = ms;
+    if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) acc.resolve_ms = ms;
+    if (hipEventElapsedTime(&ms, ev[0], ev[2]) == hipSuccess) acc.total_ms = ms;
+    acc.batches = (uint32_t) n_it;
+  }
+  for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
+  if (rc) return fail(FJGPU_ENODEV, std::string("fjgpu_denoise: HIP failure: ") + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
+  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string("fjgpu_denoise: stream synchronize: ") + hipGetErrorString(se));
+  if (stats) *stats = acc;
   return 0;
 }
 

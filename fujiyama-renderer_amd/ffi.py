@@ -58,6 +58,16 @@ class AovBuffers(C.Structure):         # fjgpu_aov_buffers: DEVICE pointers, 0 =
     _fields_ = [(n, C.c_void_p) for n in ("depth", "position", "normal", "uv", "ids", "coverage")]
 
 
+class DenoiseDesc(C.Structure):       # fjgpu_denoise_desc
+    _fields_ = [
+        ("xres", C.c_int32), ("yres", C.c_int32),
+        ("region", C.c_int32 * 4),
+        ("iterations", C.c_int32),
+        ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+        ("stop_at_ids", C.c_int32),
+    ]
+
+
 class RenderStats(C.Structure):        # fj_render_stats
     _fields_ = [("render_seconds", C.c_double), ("prepare_seconds", C.c_double), ("rays", RayCounts)]
 

@@ -35,6 +35,8 @@ def lib():
         L.fjgpu_unpack_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.fjgpu_render_aov.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_void_p, C.c_int, C.POINTER(ffi.AovBuffers),
                                        C.c_void_p, C.POINTER(ffi.GpuStats)]
+        L.fjgpu_denoise.argtypes = [C.c_int, C.POINTER(ffi.DenoiseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.POINTER(ffi.GpuStats)]
         L.fjgpu_camera_samples.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_int, C.c_void_p, C.c_int]
         L.fjgpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.fjgpu_global_option.argtypes = [C.c_char_p, C.c_long]
@@ -122,6 +124,11 @@ class Scene(object):
         depth [1] f32, position [3], normal [3], uv [2], ids [4] int32 (instance, primitive, shading group, shader index),
         coverage [1].  The buffers are torch tensors on the scene's device; `prefill` (a number, or {name: number}) sets every
         element beforehand, so that the pixels of tiles not listed can be told from those written (default 0)."""
+        tensors, st = self._render_aov_device(render, tile_ids, want, prefill, stream)
+        return {name: t.cpu().numpy() for name, t in tensors.items()}, st
+
+    def _render_aov_device(self, render, tile_ids=None, want=AOV_NAMES, prefill=None, stream=None):
+        """render_aov with the buffers left where the pass wrote them -> ({name: torch tensor on the scene's device}, GpuStats)"""
         import torch
         want = tuple(want)
         for name in want:
@@ -143,7 +150,42 @@ class Scene(object):
             ids = np.ascontiguousarray(tile_ids, dtype=np.int32)
             ids_p, n = ids.ctypes.data_as(C.c_void_p), len(ids)
         _check(lib().fjgpu_render_aov(self._h, C.byref(render), ids_p, n, C.byref(bufs), C.c_void_p(stream or 0), C.byref(st)))
-        return {name: t.cpu().numpy() for name, t in tensors.items()}, st
+        return tensors, st
+
+    def render_denoised(self, render, keep_inputs=False, stream=None, **kw):
+        """A beauty frame, its feature buffers and the denoiser (include/fjgpu.h: fjgpu_denoise) in one go, everything on the device:
+        render_tiles into a device framebuffer, render_aov(want=("position", "normal", "ids")), denoise over the render region; the
+        only copy to the host is the result's.  -> (numpy [H, W, 4] float32, info) with info["beauty_stats"], info["aov_stats"],
+        info["denoise_stats"] (GpuStats), info["sigma_position"] (the value used) and, with keep_inputs, info["beauty"] and
+        info["aov"] (numpy copies of what the filter read).  `kw` are denoise()'s parameters.  Where sigma_position is not given it
+        is SIGMA_POSITION_FRACTION of the diagonal of the bounding box of the finite positions of the foreground pixels (ids[0] >= 0)
+        of the region; a frame without foreground switches the term off.  The AOV pass's refusals (adaptive sampler, time-sampled
+        camera, scene with motion) pass through unchanged."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        region = tuple(int(v) for v in render.region)
+        if "region" in kw:
+            raise ValueError("render_denoised filters the render region of `render`")
+        fb = torch.zeros((render.yres, render.xres, 4), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)          # the fill ran on torch's stream
+        st_beauty = self.render_tiles(render, None, fb.data_ptr(), stream=stream)
+        aov, st_aov = self._render_aov_device(render, want=("position", "normal", "ids"), stream=stream)
+        if kw.get("sigma_position") is None:
+            x0, y0, x1, y1 = region
+            pos = aov["position"][y0:y1, x0:x1].reshape(-1, 3)
+            keep = (aov["ids"][y0:y1, x0:x1, 0].reshape(-1) >= 0) & torch.isfinite(pos).all(dim=1)
+            if bool(keep.any()):
+                p = pos[keep].double()
+                kw["sigma_position"] = SIGMA_POSITION_FRACTION * float(torch.linalg.norm(p.max(dim=0).values - p.min(dim=0).values))
+            else:
+                kw["sigma_position"] = 0.0
+        info = dict(beauty_stats=st_beauty, aov_stats=st_aov, sigma_position=kw["sigma_position"])
+        if keep_inputs:
+            info["beauty"] = fb.cpu().numpy()
+            info["aov"] = {name: t.cpu().numpy() for name, t in aov.items()}
+        out, info["denoise_stats"] = denoise(fb, aov["normal"], aov["position"], aov["ids"], region=region, device=self._device,
+                                             stream=stream, out=fb, **kw)
+        return out, info
 
     def camera_samples(self, render, tile_id):
         """the camera rays of one tile as the AOV and beauty passes trace them (include/fjgpu.h: fjgpu_camera_samples) ->
@@ -209,6 +251,59 @@ def host_instance_level(scene_desc_ptr, group):
     _check(min(0, L.fjgpu_host_instance_level(scene_desc_ptr, group, inst.ctypes.data_as(C.c_void_p), skip.ctypes.data_as(C.c_void_p),
                                               box.ctypes.data_as(C.c_void_p), n)))
     return inst, skip, box
+
+
+# the denoiser's defaults: of the grid in profiles/denoise_pass.txt (the 64 x 48 Cornell box at 2 x 2 spp against a 12 x 12 spp frame, CPU
+# oracle and numpy model) the setting with the smallest mean squared error among those that stop at instance ids
+DENOISE_ITERATIONS = 5
+SIGMA_COLOR = 3.0
+SIGMA_NORMAL = 1.0
+SIGMA_POSITION_FRACTION = 0.1       # of the diagonal of the foreground's bounding box (Scene.render_denoised)
+
+
+def _device_tensor(a, name, dtype, channels, dev, shape=None):
+    import torch
+    if a is None:
+        return None
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    t = t.to(device=dev, dtype=dtype).contiguous()
+    if t.dim() != 3 or t.shape[2] != channels or (shape is not None and tuple(t.shape[:2]) != tuple(shape)):
+        raise ValueError("%s must be [H, W, %d]%s, not %s" % (name, channels, "" if shape is None else " with H, W = %d, %d" % tuple(shape),
+                                                             tuple(t.shape)))
+    return t
+
+
+def denoise(color, normal=None, position=None, ids=None, iterations=DENOISE_ITERATIONS, sigma_color=SIGMA_COLOR,
+            sigma_normal=SIGMA_NORMAL, sigma_position=None, stop_at_ids=True, region=None, device=0, stream=None, out=None):
+    """Edge-avoiding a-trous filter of a beauty frame (include/fjgpu.h: fjgpu_denoise) -> (numpy [H, W, 4] float32, GpuStats).
+    color [H, W, 4] RGBA, normal / position [H, W, 3], ids [H, W, 4] int32 (the buffers of Scene.render_aov): numpy arrays, which
+    are uploaded, or torch tensors on the device, which are used where they are.  A sigma <= 0 or +inf switches its term off;
+    sigma_position is in world units (None: off -- Scene.render_denoised derives one from the scene's size).  region = (xmin, ymin,
+    xmax, ymax), None = the frame; pixels outside it are the input's.  out: a float32 device tensor [H, W, 4] to write instead of
+    a new one -- it may be `color` itself (in place) -- whose pixels outside the region are left as they are."""
+    import torch
+    dev = torch.device("cuda", device)
+    c = _device_tensor(color, "color", torch.float32, 4, dev)
+    hw = tuple(c.shape[:2])
+    n = _device_tensor(normal, "normal", torch.float32, 3, dev, hw)
+    p = _device_tensor(position, "position", torch.float32, 3, dev, hw)
+    i = _device_tensor(ids, "ids", torch.int32, 4, dev, hw)
+    if out is None:
+        out = c.clone()
+    elif not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(c.shape)):
+        raise ValueError("out must be a contiguous float32 tensor of color's shape on the device")
+    d = ffi.DenoiseDesc()
+    d.yres, d.xres = hw
+    d.region[:] = (0, 0, d.xres, d.yres) if region is None else tuple(int(v) for v in region)
+    d.iterations = int(iterations)
+    d.sigma_color, d.sigma_normal = float(sigma_color), float(sigma_normal)
+    d.sigma_position = 0.0 if sigma_position is None else float(sigma_position)
+    d.stop_at_ids = 1 if stop_at_ids else 0
+    torch.cuda.synchronize(dev)          # uploads and copies ran on torch's stream
+    st = ffi.GpuStats()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _check(lib().fjgpu_denoise(device, C.byref(d), ptr(c), ptr(n), ptr(p), ptr(i), ptr(out), C.c_void_p(stream or 0), C.byref(st)))
+    return out.cpu().numpy(), st
 
 
 def global_option(name, value):

@@ -193,6 +193,47 @@ int fjgpu_render_aov(fjgpu_scene *scene, const fj_render_desc *render, const int
  * negative error (the refusals of fjgpu_render_aov). */
 int fjgpu_camera_samples(fjgpu_scene *scene, const fj_render_desc *render, int tile_id, double *rays8, int cap);
 
+/* Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010) over a beauty frame, guided by the
+ * feature buffers of fjgpu_render_aov.  Device buffers in, device buffers out; no scene handle.  A spatial filter of ONE frame: no albedo
+ * demodulation (textured surfaces lean on the colour term), no variance guidance, no temporal reuse.
+ *
+ * All arithmetic is f32 without fused multiply-adds, sums left to right (csrc/device/fjgpu_denoise_math.h is the one source of the
+ * kernel, of the host twin the CPU tests run and of the constants).  h = (1/16, 1/4, 3/8, 1/4, 1/16).  For iteration i = 0 ..
+ * iterations-1 with s = 2^i, C = color_in (i = 0) or the previous iteration's output, and every region pixel p: the taps q = p + s (dx, dy),
+ * dy = -2..2 (outer), dx = -2..2 (inner).  A tap outside the region is skipped; with stop_at_ids a tap with ids[q][0] != ids[p][0] is
+ * skipped (background, -1, is an id like any other: it never bleeds into geometry).  Otherwise
+ *   d2c = (Cq.r-Cp.r)^2 + (Cq.g-Cp.g)^2 + (Cq.b-Cp.b)^2, d2n and d2x likewise from normal and position,
+ *   e = d2c k_c + d2n k_n + d2x k_x,  w = (h[dy+2] h[dx+2]) expf(-e)     (one expf per tap, of the summed exponent)
+ *   sum += w Cq over all four channels (alpha is filtered with the same weights), wsum += w;   out_p = sum / wsum
+ * (the centre tap contributes 9/64, so wsum > 0).  k_c = (float) (1 / (sigma_color 2^-i)^2), k_n = (float) (1 / sigma_normal^2),
+ * k_x = (float) (1 / sigma_position^2), computed in f64 and rounded once (capped at FLT_MAX); k = 0 for a term that is off.
+ *
+ * Only pixels of the region are read and written; pixels of color_out outside it stay untouched.  color_out may EQUAL color_in (any
+ * other overlap of the two is not allowed); both must be 16-byte aligned.  The inputs must be finite, and so must the squared
+ * differences of neighbouring pixels (a NaN or an infinity spreads over the filter's support).
+ * Scratch is allocated per call and freed before the call returns: two RGBA frames of the region and one 32-byte guide record per region
+ * pixel.  Work is enqueued on `hip_stream` and the call returns after the stream has been synchronised.  stats (may be NULL): gen_ms (the
+ * guide pack), resolve_ms (the filter iterations), total_ms, batches = iterations.
+ * Errors: FJGPU_EINVAL, the message naming fjgpu_denoise, for a NULL desc / color_in / color_out, an invalid region, iterations outside
+ * 1..8, a NaN sigma, a misaligned colour pointer; FJGPU_ENODEV when no device is visible. */
+typedef struct fjgpu_denoise_desc {
+  int32_t xres, yres;          /* row-major frame the buffers describe                                   */
+  int32_t region[4];           /* xmin ymin xmax ymax, the convention (and validation) of fj_render_desc */
+  int32_t iterations;          /* 1..8; iteration i uses tap spacing 2^i                                 */
+  float   sigma_color;         /* > 0, or <= 0 / +inf: term off; halves every iteration                  */
+  float   sigma_normal;        /* likewise; ignored where `normal` is NULL                               */
+  float   sigma_position;      /* likewise, world units; ignored where `position` is NULL                */
+  int32_t stop_at_ids;         /* 1: a tap whose instance id (ids[0]) differs from the centre's weighs 0 */
+} fjgpu_denoise_desc;
+
+int fjgpu_denoise(int device, const fjgpu_denoise_desc *desc,
+                  const float *color_in,   /* DEVICE [yres][xres][4] RGBA f32                */
+                  const float *normal,     /* DEVICE [.][.][3] or NULL                       */
+                  const float *position,   /* DEVICE [.][.][3] or NULL                       */
+                  const int32_t *ids,      /* DEVICE [.][.][4] or NULL (then stop_at_ids = 0)*/
+                  float *color_out,        /* DEVICE [.][.][4]; may equal color_in           */
+                  void *hip_stream, fjgpu_stats *stats);
+
 /* Tunables (all have defaults): "batch_tiles" tiles per wavefront batch, "batch_samples" samples per batch where batch_tiles is 0
  * (0, the default: as many as the memory budget holds -- fastest where frames repeat; a caller that renders one frame per scene
  * sets a few M: the work arena shrinks from ~110 GB to a few GB at the headline size and the cold frame starts sooner),
