@@ -2096,15 +2096,17 @@ static TileDesc aov_tile(const fj_render_desc *r, const fjgpu::TileRect &t, cons
   return d;
 }
 
-int fjgpu_render_aov(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
-    const fjgpu_aov_buffers *out, void *hip_stream, fjgpu_stats *stats)
+// the body of fjgpu_render_aov and fjgpu_render_aov_albedo: one camera-ray generation and one closest-hit walk per batch, then k_aov_reduce
+// where a member of `out` is set, then k_aov_albedo where d_albedo is set.  `who` is the entry point's name in the messages.
+static int render_aov_body(const char *who_, fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
+    const fjgpu_aov_buffers *out, float *d_albedo, void *hip_stream, fjgpu_stats *stats)
 {
-  if (!sc || !r || !out) return fail(FJGPU_EINVAL, "fjgpu_render_aov: null argument");
-  if (!out->depth && !out->position && !out->normal && !out->uv && !out->ids && !out->coverage)
-    return fail(FJGPU_EINVAL, "fjgpu_render_aov: every buffer pointer is NULL, nothing to write");
-  if (tile_ids && n_tiles < 0) return fail(FJGPU_EINVAL, "fjgpu_render_aov: negative tile count");
+  const std::string who(who_);
+  const bool reduce = out && (out->depth || out->position || out->normal || out->uv || out->ids || out->coverage);
+  if (!reduce && !d_albedo) return fail(FJGPU_EINVAL, who + ": every buffer pointer is NULL, nothing to write");
+  if (tile_ids && n_tiles < 0) return fail(FJGPU_EINVAL, who + ": negative tile count");
   AovSetup A;
-  if (const int e = aov_setup(sc, r, "fjgpu_render_aov", &A)) return e;
+  if (const int e = aov_setup(sc, r, who_, &A)) return e;
   HIP_TRY(hipSetDevice(sc->device));
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
 
@@ -2126,7 +2128,7 @@ int fjgpu_render_aov(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *ti
     const fjgpu::TileRect &t = A.all[ids[k]];
     TileDesc d = aov_tile(r, t, A.margin, 0);
     const size_t ts = (size_t) d.nx * (size_t) d.ny;
-    if (ts > 0x7fffffffu) return fail(FJGPU_EINVAL, "fjgpu_render_aov: a tile of more than 2^31 samples: lower the tilesize");
+    if (ts > 0x7fffffffu) return fail(FJGPU_EINVAL, who + ": a tile of more than 2^31 samples: lower the tilesize");
     if (batches.empty() || batches.back().n >= 65535 || (size_t) batches.back().samples + ts > limit) batches.push_back(Batch{k, 0, 0u, 0u, 0});
     Batch &b = batches.back();
     d.sample_offset = b.samples;
@@ -2143,12 +2145,12 @@ int fjgpu_render_aov(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *ti
   const double *d_jit = nullptr;
   if (W.alloc(cap_samples * 2, &d_suv) || W.alloc(cap_samples, &d_rays) || W.alloc(cap_samples, &d_paths) || W.alloc(cap_samples, &d_hits) ||
       W.alloc(1, &d_cnt) || W.alloc(td.size(), &d_tiles))
-    return fail(FJGPU_ENOMEM, "fjgpu_render_aov: device allocation failed: lower the aov_batch_samples option");
+    return fail(FJGPU_ENOMEM, who + ": device allocation failed: lower the aov_batch_samples option");
   {
     // the per-tile XorShift stream as a table (draw k is the same number in every tile): two draws per sample of the largest tile
     std::vector<double> draws;
     fjgpu::XorShiftTable(2 * tab_len, &draws);
-    if (W.upload(draws.data(), 2 * tab_len, &d_jit)) return fail(FJGPU_ENOMEM, "fjgpu_render_aov: device allocation failed");
+    if (W.upload(draws.data(), 2 * tab_len, &d_jit)) return fail(FJGPU_ENOMEM, who + ": device allocation failed");
   }
   HIP_TRY(hipMemcpy(d_tiles, td.data(), sizeof(TileDesc) * td.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(d_cnt, 0, sizeof(DCounters)));
@@ -2156,7 +2158,13 @@ int fjgpu_render_aov(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *ti
   S.time_tab = d_jit;      // (never read: no motion, a static camera)
   AovParams ap;
   ap.xres = r->xres; ap.rate_x = r->rate_x; ap.rate_y = r->rate_y; ap.margin_x = A.margin[0]; ap.margin_y = A.margin[1]; ap.pad = 0;
-  ap.depth = out->depth; ap.position = out->position; ap.normal = out->normal; ap.uv = out->uv; ap.ids = out->ids; ap.coverage = out->coverage;
+  ap.depth = ap.position = ap.normal = ap.uv = ap.coverage = nullptr; ap.ids = nullptr;
+  if (reduce) { ap.depth = out->depth; ap.position = out->position; ap.normal = out->normal; ap.uv = out->uv; ap.ids = out->ids; ap.coverage = out->coverage; }
+  AlbedoParams bp;
+  bp.xres = r->xres; bp.rate_x = r->rate_x; bp.rate_y = r->rate_y; bp.margin_x = A.margin[0]; bp.margin_y = A.margin[1]; bp.pad = 0;
+  bp.lanes = 1; bp.lanes_log2 = 0;      // lanes per pixel: the smallest power of two >= min(samples per pixel, 64)
+  while (bp.lanes < 64 && (long) bp.lanes < (long) r->rate_x * r->rate_y) { bp.lanes <<= 1; bp.lanes_log2++; }
+  bp.albedo = d_albedo;
 
   // event pairs around every launch, turned into durations after the one synchronisation at the end
   struct Span { hipEvent_t a, b; double *bucket; };
@@ -2186,7 +2194,9 @@ int fjgpu_render_aov(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *ti
     if (rc) break;
     rc = timed(&acc.closest_ms, [&]() { return launch_trace_closest(st, S, d_rays, d_paths, d_hits, B.samples, d_cnt, (int) sc->count_events); });
     if (rc) break;
-    rc = timed(&acc.resolve_ms, [&]() { return launch_aov_reduce(st, S, ap, tiles, B.n, B.max_px, d_rays, d_hits); });
+    if (reduce) rc = timed(&acc.resolve_ms, [&]() { return launch_aov_reduce(st, S, ap, tiles, B.n, B.max_px, d_rays, d_hits); });
+    if (rc) break;
+    if (d_albedo) rc = timed(&acc.resolve_ms, [&]() { return launch_aov_albedo(st, S, bp, tiles, B.n, B.max_px, d_hits); });
     if (rc) break;
     acc.rays.camera += B.samples;
     acc.trace_launches++; acc.closest_launches++; acc.batches++;
@@ -2200,8 +2210,8 @@ int fjgpu_render_aov(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *ti
     acc.trace_ms = acc.closest_ms;
   }
   drop_events();
-  if (rc) return fail(FJGPU_ENODEV, std::string("fjgpu_render_aov: HIP failure: ") + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
-  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string("fjgpu_render_aov: stream synchronize: ") + hipGetErrorString(se));
+  if (rc) return fail(FJGPU_ENODEV, who + ": HIP failure: " + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
+  if (se != hipSuccess) return fail(FJGPU_ENODEV, who + ": stream synchronize: " + hipGetErrorString(se));
   if (stats) {
     DCounters hc;
     HIP_TRY(hipMemcpy(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost));
@@ -2211,13 +2221,30 @@ int fjgpu_render_aov(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *ti
   return 0;
 }
 
+int fjgpu_render_aov(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
+    const fjgpu_aov_buffers *out, void *hip_stream, fjgpu_stats *stats)
+{
+  if (!sc || !r || !out) return fail(FJGPU_EINVAL, "fjgpu_render_aov: null argument");
+  return render_aov_body("fjgpu_render_aov", sc, r, tile_ids, n_tiles, out, nullptr, hip_stream, stats);
+}
+
+int fjgpu_render_aov_albedo(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
+    const fjgpu_aov_buffers *out, float *d_albedo, void *hip_stream, fjgpu_stats *stats)
+{
+  if (!sc || !r) return fail(FJGPU_EINVAL, "fjgpu_render_aov_albedo: null argument (scene and render are required)");
+  return render_aov_body("fjgpu_render_aov_albedo", sc, r, tile_ids, n_tiles, out, d_albedo, hip_stream, stats);
+}
+
 // ---- denoiser (fjgpu_denoise.hip, fjgpu_denoise_math.h).  Shaped like the AOV pass: no scene, transient buffers per call -- two RGBA frames
 // of the region for the iterations to ping-pong between and one 32-byte guide record per region pixel.  Iteration 0 reads color_in and the
 // last one writes color_out, every other end of an iteration is a scratch frame, so color_out may be color_in: with two or more iterations
 // no launch reads what it writes, and a single iteration in place filters a copy of the region.
-int fjgpu_denoise(int device, const fjgpu_denoise_desc *d, const float *color_in, const float *normal, const float *position,
-    const int32_t *ids, float *color_out, void *hip_stream, fjgpu_stats *stats)
+// (the refusals keep fjgpu_denoise's name in their messages, whichever of the two entry points was called: with albedo NULL they are the same call)
+int fjgpu_denoise_albedo(int device, const fjgpu_denoise_desc *d, const float *color_in, const float *normal, const float *position,
+    const int32_t *ids, const float *albedo, float albedo_floor, float *color_out, void *hip_stream, fjgpu_stats *stats)
 {
+  if (albedo && !(std::isfinite(albedo_floor) && albedo_floor > 0))
+    return fail(FJGPU_EINVAL, "fjgpu_denoise_albedo: albedo_floor must be finite and > 0");
   if (!d || !color_in || !color_out) return fail(FJGPU_EINVAL, "fjgpu_denoise: null argument (desc, color_in and color_out are required)");
   if (d->xres <= 0 || d->yres <= 0) return fail(FJGPU_EINVAL, "fjgpu_denoise: resolution must be positive");
   if (d->region[0] < 0 || d->region[1] < 0 || d->region[2] > d->xres || d->region[3] > d->yres ||
@@ -2254,7 +2281,12 @@ int fjgpu_denoise(int device, const fjgpu_denoise_desc *d, const float *color_in
   }
   const float *src = color_in + origin;
   int src_stride = d->xres;
-  if (!rc && n_it == 1 && color_in == color_out) {
+  if (!rc && albedo) {
+    // the filter's input is colour / albedo, staged in the scratch frame iteration 0 does not write (iteration 1 is the first to)
+    rc = launch_dn_demodulate(st, src, d->xres, albedo, d->xres, d->region[0], d->region[1], albedo_floor, d_frame[1], w, w, h);
+    src = d_frame[1]; src_stride = w;
+    if (ev[1]) (void) hipEventRecord(ev[1], st);      // (gen_ms: the guide pack and this copy)
+  } else if (!rc && n_it == 1 && color_in == color_out) {
     // in place with a single iteration: that launch would read pixels other blocks have written
     if (hipMemcpy2DAsync(d_frame[1], (size_t) w * 16, src, (size_t) d->xres * 16, (size_t) w * 16, (size_t) h, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = -1;
     src = d_frame[1]; src_stride = w;
@@ -2267,6 +2299,7 @@ int fjgpu_denoise(int device, const fjgpu_denoise_desc *d, const float *color_in
                           fj_dn_constants(d->sigma_color, normal ? d->sigma_normal : 0.f, position ? d->sigma_position : 0.f, i));
     src = dst; src_stride = dst_stride;
   }
+  if (!rc && albedo) rc = launch_dn_remodulate(st, color_out + origin, d->xres, albedo, d->xres, d->region[0], d->region[1], albedo_floor, w, h);
   if (ev[2]) (void) hipEventRecord(ev[2], st);
   const hipError_t se = hipStreamSynchronize(st);      // (also before the transient buffers go away)
   if (rc == 0 && se == hipSuccess) {
@@ -2281,6 +2314,12 @@ int fjgpu_denoise(int device, const fjgpu_denoise_desc *d, const float *color_in
   if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string("fjgpu_denoise: stream synchronize: ") + hipGetErrorString(se));
   if (stats) *stats = acc;
   return 0;
+}
+
+int fjgpu_denoise(int device, const fjgpu_denoise_desc *d, const float *color_in, const float *normal, const float *position,
+    const int32_t *ids, float *color_out, void *hip_stream, fjgpu_stats *stats)
+{
+  return fjgpu_denoise_albedo(device, d, color_in, normal, position, ids, nullptr, 0.f, color_out, hip_stream, stats);
 }
 
 int fjgpu_camera_samples(fjgpu_scene *sc, const fj_render_desc *r, int tile_id, double *rays8, int cap)

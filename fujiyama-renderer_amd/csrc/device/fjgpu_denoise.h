@@ -17,4 +17,12 @@ int launch_dn_pack(hipStream_t st, const float *normal, const float *position, c
 int launch_dn_atrous(hipStream_t st, const float *src, int src_stride, const float *guide, float *dst, int dst_stride,
     int w, int h, int spacing, int stop_at_ids, DnConst k);
 
+// albedo demodulation around the iterations (fjgpu_denoise_albedo).  `albedo` is frame-sized ([.][xres][3]); (xmin, ymin) the region's corner.
+// demodulate: the region of src (src_stride pixels per row, pointing at the region's first pixel) -> dst (dst_stride), rgb divided by the
+// clamped albedo, alpha copied; src and dst must not overlap.  remodulate: rgb of the region of `color` multiplied by it, in place.
+int launch_dn_demodulate(hipStream_t st, const float *src, int src_stride, const float *albedo, int xres, int xmin, int ymin,
+    float albedo_floor, float *dst, int dst_stride, int w, int h);
+int launch_dn_remodulate(hipStream_t st, float *color, int stride, const float *albedo, int xres, int xmin, int ymin,
+    float albedo_floor, int w, int h);
+
 #endif

@@ -10,6 +10,8 @@
 //                the wave.  The centre pixel stays in registers.  No atomics, no scratch memory; a block talks to no other.
 //   k_dn_atrous_tile<S>  the iterations of spacing S = 1 and 2, whose taps overlap inside a block, from an LDS-staged footprint (half the
 //                time of k_dn_atrous at those spacings on an MI355X, profiles/denoise_pass.txt; larger spacings reuse nothing inside a block).
+//   k_dn_demodulate, k_dn_remodulate  fjgpu_denoise_albedo: one lane per region pixel, rgb divided by the clamped albedo into a scratch frame
+//                before the iterations, multiplied by it in color_out after them.  One frame moved each; not fused into their neighbours.
 #include <hip/hip_runtime.h>
 
 #include "fjgpu_denoise.h"
@@ -82,6 +84,33 @@ __global__ void __launch_bounds__(DN_BX * DN_BY) k_dn_atrous(const float *src_, 
   dn_v4f o;
   o.x = s.r / s.w; o.y = s.g / s.w; o.z = s.b / s.w; o.w = s.a / s.w;
   dst[(size_t) y * (size_t) dst_stride + (size_t) x] = o;
+}
+
+__global__ void __launch_bounds__(DN_BX * DN_BY) k_dn_demodulate(const float *src_, int src_stride, const float *albedo_, int xres, int xmin, int ymin,
+    float albedo_floor, float *dst_, int dst_stride, int w, int h)
+{
+  const int x = blockIdx.x * DN_BX + threadIdx.x, y = blockIdx.y * DN_BY + threadIdx.y;
+  if (x >= w || y >= h) return;
+  const FJ_GLOBAL float *al = (const FJ_GLOBAL float *) albedo_ + 3 * ((size_t) (ymin + y) * (size_t) xres + (size_t) (xmin + x));
+  dn_v4f c = ((const FJ_GLOBAL dn_v4f *) src_)[(size_t) y * (size_t) src_stride + (size_t) x];
+  c.x = fj_dn_demodulate(c.x, fj_dn_albedo_clamp(al[0], albedo_floor));
+  c.y = fj_dn_demodulate(c.y, fj_dn_albedo_clamp(al[1], albedo_floor));
+  c.z = fj_dn_demodulate(c.z, fj_dn_albedo_clamp(al[2], albedo_floor));
+  ((FJ_GLOBAL dn_v4f *) dst_)[(size_t) y * (size_t) dst_stride + (size_t) x] = c;
+}
+
+__global__ void __launch_bounds__(DN_BX * DN_BY) k_dn_remodulate(float *color_, int stride, const float *albedo_, int xres, int xmin, int ymin,
+    float albedo_floor, int w, int h)
+{
+  const int x = blockIdx.x * DN_BX + threadIdx.x, y = blockIdx.y * DN_BY + threadIdx.y;
+  if (x >= w || y >= h) return;
+  const FJ_GLOBAL float *al = (const FJ_GLOBAL float *) albedo_ + 3 * ((size_t) (ymin + y) * (size_t) xres + (size_t) (xmin + x));
+  FJ_GLOBAL dn_v4f *p = (FJ_GLOBAL dn_v4f *) color_ + ((size_t) y * (size_t) stride + (size_t) x);
+  dn_v4f c = *p;
+  c.x = fj_dn_remodulate(c.x, fj_dn_albedo_clamp(al[0], albedo_floor));
+  c.y = fj_dn_remodulate(c.y, fj_dn_albedo_clamp(al[1], albedo_floor));
+  c.z = fj_dn_remodulate(c.z, fj_dn_albedo_clamp(al[2], albedo_floor));
+  *p = c;
 }
 
 #if FJ_DN_LDS_TILE
@@ -163,5 +192,25 @@ int launch_dn_atrous(hipStream_t st, const float *src, int src_stride, const flo
   else
 #endif
   hipLaunchKernelGGL(k_dn_atrous, grid, dim3(DN_BX, DN_BY), 0, st, src, src_stride, guide, dst, dst_stride, w, h, spacing, stop_at_ids, k);
+  return (int) hipGetLastError();
+}
+
+int launch_dn_demodulate(hipStream_t st, const float *src, int src_stride, const float *albedo, int xres, int xmin, int ymin,
+    float albedo_floor, float *dst, int dst_stride, int w, int h)
+{
+  if (w <= 0 || h <= 0) return 0;
+  const dim3 grid((w + DN_BX - 1) / DN_BX, (h + DN_BY - 1) / DN_BY);
+  if (grid.y > 65535u) return (int) hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(k_dn_demodulate, grid, dim3(DN_BX, DN_BY), 0, st, src, src_stride, albedo, xres, xmin, ymin, albedo_floor, dst, dst_stride, w, h);
+  return (int) hipGetLastError();
+}
+
+int launch_dn_remodulate(hipStream_t st, float *color, int stride, const float *albedo, int xres, int xmin, int ymin,
+    float albedo_floor, int w, int h)
+{
+  if (w <= 0 || h <= 0) return 0;
+  const dim3 grid((w + DN_BX - 1) / DN_BX, (h + DN_BY - 1) / DN_BY);
+  if (grid.y > 65535u) return (int) hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(k_dn_remodulate, grid, dim3(DN_BX, DN_BY), 0, st, color, stride, albedo, xres, xmin, ymin, albedo_floor, w, h);
   return (int) hipGetLastError();
 }

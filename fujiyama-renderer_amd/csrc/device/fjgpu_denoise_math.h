@@ -90,4 +90,10 @@ FJ_DN_FN void fj_dn_tap(DnAccum &s, int dx, int dy, const DnPixel &p, const DnPi
   s.w += w;
 }
 
+// ---- albedo demodulation (fjgpu_denoise_albedo): the filter runs on colour / albedo, the albedo is multiplied back afterwards.  Each of the
+// three is ONE correctly rounded f32 operation per value (a NaN albedo takes the floor)
+FJ_DN_FN float fj_dn_albedo_clamp(float albedo, float albedo_floor) { return albedo > albedo_floor ? albedo : albedo_floor; }
+FJ_DN_FN float fj_dn_demodulate(float c, float a) { return c / a; }
+FJ_DN_FN float fj_dn_remodulate(float f, float a) { return f * a; }
+
 #endif

@@ -27,6 +27,12 @@ struct AovParams {             // fjgpu_render_aov: the reduce kernel's view of 
   float *coverage;
 };
 
+struct AlbedoParams {          // fjgpu_render_aov_albedo: the albedo kernel's view of the call (fjgpu_dev_albedo.h)
+  int32_t xres, rate_x, rate_y, margin_x, margin_y;
+  int32_t lanes, lanes_log2, pad;   // lanes per pixel: the smallest power of two >= min(rate_x * rate_y, 64)
+  float *albedo;               // DEVICE [yres][xres][3]
+};
+
 struct AdaptiveParams {       // AdaptiveGridSampler, src/fj_adaptive_grid_sampler.cc
   int32_t D, div;              // adaptive_max_subdivision, 2^D lattice cells per pixel
   int32_t margin_x, margin_y;  // filter margin in PIXELS: ceil(filterwidth - 1)
@@ -95,6 +101,10 @@ int launch_resolve(hipStream_t st, const ResolveParams &rp, const TileDesc *d_ti
 // first-hit AOV pass (fjgpu_dev_aov.h): the own samples of every pixel of the batch's tiles reduced to the nearest hit, its attributes written out
 int launch_aov_reduce(hipStream_t st, const DScene &S, const AovParams &ap, const TileDesc *d_tiles, int n_tiles, int max_tile_pixels,
     const DRay *rays, const DHit *hits);
+
+// albedo AOV (fjgpu_dev_albedo.h): the mean surface colour of every pixel's own samples, from the hit records of the batch k_aov_reduce read
+int launch_aov_albedo(hipStream_t st, const DScene &S, const AlbedoParams &ap, const TileDesc *d_tiles, int n_tiles, int max_tile_pixels,
+    const DHit *hits);
 
 // adaptive grid sampler (fjgpu_dev_adaptive.h)
 int launch_adaptive_uv(hipStream_t st, const AdaptiveParams &ap, const TileDesc *d_tiles, int n_tiles, uint32_t max_tile_samples,

@@ -15,6 +15,7 @@
 //   fjgpu_dev_anyhit.h    k_shadow_anyhit (lean any-hit walk: phase-scheduled, f32 slabs)
 //   fjgpu_dev_anyhit_curves.h  k_shadow_anyhit_curves (the same scheduling for scenes with curve sets: + a ribbon phase)
 //   fjgpu_dev_aov.h       k_aov_reduce (fjgpu_render_aov: nearest own sample of every pixel, its hit attributes written out)
+//   fjgpu_dev_albedo.h    k_aov_albedo (fjgpu_render_aov_albedo: the mean albedo of every pixel's own samples)
 //   fjgpu_dev_flat.h      k_trace_closest_flat (closest-hit walk of FLAT groups: one world-space culling tree per group, exact tests in object space)
 //   here                  k_resolve (reconstruct_image / apply_pixel_filter), host launchers
 #include <hip/hip_runtime.h>
@@ -41,6 +42,7 @@
 #include "fjgpu_dev_anyhit_curves.h"
 #include "fjgpu_dev_adaptive.h"
 #include "fjgpu_dev_aov.h"
+#include "fjgpu_dev_albedo.h"
 
 // ------------------------------------------------------------------ k_resolve
 // reconstruct_image + apply_pixel_filter (src/fj_renderer.cc:939-995) with
@@ -529,6 +531,18 @@ int launch_aov_reduce(hipStream_t st, const DScene &S, const AovParams &ap, cons
   if (n_tiles <= 0 || max_tile_pixels <= 0) return 0;
   const dim3 grid((max_tile_pixels + BLOCK / 64 - 1) / (BLOCK / 64), n_tiles);      // one wave per pixel
   hipLaunchKernelGGL(k_aov_reduce, grid, dim3(BLOCK), 0, st, S, ap, d_tiles, rays, hits);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_aov_albedo(hipStream_t st, const DScene &S, const AlbedoParams &ap, const TileDesc *d_tiles, int n_tiles, int max_tile_pixels,
+    const DHit *hits)
+{
+  if (n_tiles <= 0 || max_tile_pixels <= 0) return 0;
+  if (ap.lanes < 1 || ap.lanes > 64 || ap.lanes != (1 << ap.lanes_log2)) return (int) hipErrorInvalidValue;
+  const int per_wave = 64 / ap.lanes, per_block = per_wave * (BLOCK / 64);      // a group of `lanes` lanes per pixel
+  const dim3 grid((max_tile_pixels + per_block - 1) / per_block, n_tiles);
+  hipLaunchKernelGGL(k_aov_albedo, grid, dim3(BLOCK), 0, st, S, ap, d_tiles, hits);
   LAUNCH_CHECK();
   return 0;
 }

@@ -67,6 +67,34 @@ int fj_denoise_host(const fjgpu_denoise_desc *d, const float *color_in, const fl
   return 0;
 }
 
+// the arguments of fjgpu_denoise_albedo on host memory: the region's rgb divided by the clamped albedo, the loop above, the albedo multiplied
+// back -- the three steps through the functions k_dn_demodulate / k_dn_remodulate compile.  albedo NULL: fj_denoise_host.
+int fj_denoise_albedo_host(const fjgpu_denoise_desc *d, const float *color_in, const float *normal, const float *position, const int32_t *ids,
+    const float *albedo, float albedo_floor, float *color_out)
+{
+  if (!albedo) return fj_denoise_host(d, color_in, normal, position, ids, color_out);
+  if (!(isfinite(albedo_floor) && albedo_floor > 0)) return FJGPU_EINVAL;
+  if (!d || !color_in || !color_out) return FJGPU_EINVAL;
+  if (d->xres <= 0 || d->yres <= 0 || d->region[0] < 0 || d->region[1] < 0 || d->region[2] > d->xres || d->region[3] > d->yres ||
+      d->region[0] >= d->region[2] || d->region[1] >= d->region[3])
+    return FJGPU_EINVAL;
+  // a frame-sized copy whose region is demodulated (only the region is read by the loop)
+  std::vector<float> dem((size_t) d->xres * d->yres * 4);
+  for (int y = d->region[1]; y < d->region[3]; y++)
+    for (int x = d->region[0]; x < d->region[2]; x++) {
+      const size_t at = (size_t) y * d->xres + x;
+      for (int k = 0; k < 3; k++) dem[4 * at + k] = fj_dn_demodulate(color_in[4 * at + k], fj_dn_albedo_clamp(albedo[3 * at + k], albedo_floor));
+      dem[4 * at + 3] = color_in[4 * at + 3];
+    }
+  if (const int e = fj_denoise_host(d, dem.data(), normal, position, ids, color_out)) return e;
+  for (int y = d->region[1]; y < d->region[3]; y++)
+    for (int x = d->region[0]; x < d->region[2]; x++) {
+      const size_t at = (size_t) y * d->xres + x;
+      for (int k = 0; k < 3; k++) color_out[4 * at + k] = fj_dn_remodulate(color_out[4 * at + k], fj_dn_albedo_clamp(albedo[3 * at + k], albedo_floor));
+    }
+  return 0;
+}
+
 // the constants of iteration i as fjgpu_denoise passes them to the kernel: out[3] = k_c, k_n, k_x
 void fj_denoise_host_constants(float sigma_color, float sigma_normal, float sigma_position, int i, float *out)
 {

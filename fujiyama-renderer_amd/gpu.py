@@ -35,6 +35,10 @@ def lib():
         L.fjgpu_unpack_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.fjgpu_render_aov.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_void_p, C.c_int, C.POINTER(ffi.AovBuffers),
                                        C.c_void_p, C.POINTER(ffi.GpuStats)]
+        L.fjgpu_render_aov_albedo.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_void_p, C.c_int, C.POINTER(ffi.AovBuffers),
+                                              C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
+        L.fjgpu_denoise_albedo.argtypes = [C.c_int, C.POINTER(ffi.DenoiseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_float, C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
         L.fjgpu_denoise.argtypes = [C.c_int, C.POINTER(ffi.DenoiseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.POINTER(ffi.GpuStats)]
         L.fjgpu_camera_samples.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_int, C.c_void_p, C.c_int]
@@ -57,7 +61,8 @@ def device_count():
 
 
 AOV_NAMES = ("depth", "position", "normal", "uv", "ids", "coverage")       # the members of fjgpu_aov_buffers
-AOV_CHANNELS = {"depth": 1, "position": 3, "normal": 3, "uv": 2, "ids": 4, "coverage": 1}
+AOV_ALL = AOV_NAMES + ("albedo",)                                           # ... and the buffer of fjgpu_render_aov_albedo (Scene.render_aov_albedo)
+AOV_CHANNELS = {"depth": 1, "position": 3, "normal": 3, "uv": 2, "ids": 4, "coverage": 1, "albedo": 3}
 
 
 class Scene(object):
@@ -127,13 +132,21 @@ class Scene(object):
         tensors, st = self._render_aov_device(render, tile_ids, want, prefill, stream)
         return {name: t.cpu().numpy() for name, t in tensors.items()}, st
 
-    def _render_aov_device(self, render, tile_ids=None, want=AOV_NAMES, prefill=None, stream=None):
-        """render_aov with the buffers left where the pass wrote them -> ({name: torch tensor on the scene's device}, GpuStats)"""
+    def render_aov_albedo(self, render, tile_ids=None, want=AOV_ALL, prefill=None, stream=None):
+        """render_aov through the entry point that also knows "albedo" [3] f32 (include/fjgpu.h: fjgpu_render_aov_albedo): the mean
+        over the pixel's own samples of the surface colour without light, from the same camera rays and the same walk as the six
+        geometry buffers.  `want` takes any of AOV_ALL, ("albedo",) alone included; everything else is render_aov's."""
+        tensors, st = self._render_aov_device(render, tile_ids, want, prefill, stream, names=AOV_ALL)
+        return {name: t.cpu().numpy() for name, t in tensors.items()}, st
+
+    def _render_aov_device(self, render, tile_ids=None, want=AOV_NAMES, prefill=None, stream=None, names=AOV_NAMES):
+        """render_aov (names=AOV_ALL: render_aov_albedo) with the buffers left where the pass wrote them ->
+        ({name: torch tensor on the scene's device}, GpuStats)"""
         import torch
         want = tuple(want)
         for name in want:
-            if name not in AOV_NAMES:
-                raise ValueError("unknown AOV %r (one of %s)" % (name, ", ".join(AOV_NAMES)))
+            if name not in names:
+                raise ValueError("unknown AOV %r (one of %s)" % (name, ", ".join(names)))
         dev = torch.device("cuda", self._device)
         bufs = ffi.AovBuffers()
         tensors = {}
@@ -141,7 +154,8 @@ class Scene(object):
             dtype = torch.int32 if name == "ids" else torch.float32
             fill = prefill.get(name, 0) if isinstance(prefill, dict) else (0 if prefill is None else prefill)
             tensors[name] = torch.full((render.yres, render.xres, AOV_CHANNELS[name]), fill, dtype=dtype, device=dev)
-            setattr(bufs, name, tensors[name].data_ptr())
+            if name != "albedo":
+                setattr(bufs, name, tensors[name].data_ptr())
         torch.cuda.synchronize(dev)          # the fills ran on torch's stream
         st = ffi.GpuStats()
         if tile_ids is None:
@@ -149,10 +163,15 @@ class Scene(object):
         else:
             ids = np.ascontiguousarray(tile_ids, dtype=np.int32)
             ids_p, n = ids.ctypes.data_as(C.c_void_p), len(ids)
-        _check(lib().fjgpu_render_aov(self._h, C.byref(render), ids_p, n, C.byref(bufs), C.c_void_p(stream or 0), C.byref(st)))
+        if names is AOV_ALL:
+            albedo = tensors["albedo"].data_ptr() if "albedo" in tensors else None
+            _check(lib().fjgpu_render_aov_albedo(self._h, C.byref(render), ids_p, n, C.byref(bufs), C.c_void_p(albedo),
+                                                 C.c_void_p(stream or 0), C.byref(st)))
+        else:
+            _check(lib().fjgpu_render_aov(self._h, C.byref(render), ids_p, n, C.byref(bufs), C.c_void_p(stream or 0), C.byref(st)))
         return tensors, st
 
-    def render_denoised(self, render, keep_inputs=False, stream=None, **kw):
+    def render_denoised(self, render, keep_inputs=False, stream=None, demodulate=False, **kw):
         """A beauty frame, its feature buffers and the denoiser (include/fjgpu.h: fjgpu_denoise) in one go, everything on the device:
         render_tiles into a device framebuffer, render_aov(want=("position", "normal", "ids")), denoise over the render region; the
         only copy to the host is the result's.  -> (numpy [H, W, 4] float32, info) with info["beauty_stats"], info["aov_stats"],
@@ -160,7 +179,9 @@ class Scene(object):
         info["aov"] (numpy copies of what the filter read).  `kw` are denoise()'s parameters.  Where sigma_position is not given it
         is SIGMA_POSITION_FRACTION of the diagonal of the bounding box of the finite positions of the foreground pixels (ids[0] >= 0)
         of the region; a frame without foreground switches the term off.  The AOV pass's refusals (adaptive sampler, time-sampled
-        camera, scene with motion) pass through unchanged."""
+        camera, scene with motion) pass through unchanged.  demodulate=True adds "albedo" to the one AOV call (render_aov_albedo's) and filters the
+        frame divided by it (fjgpu_denoise_albedo: textures are kept out of the filter); info["aov"] then holds the albedo too and
+        info["albedo_floor"] is the value used (denoise()'s albedo_floor)."""
         import torch
         dev = torch.device("cuda", self._device)
         region = tuple(int(v) for v in render.region)
@@ -169,7 +190,10 @@ class Scene(object):
         fb = torch.zeros((render.yres, render.xres, 4), dtype=torch.float32, device=dev)
         torch.cuda.synchronize(dev)          # the fill ran on torch's stream
         st_beauty = self.render_tiles(render, None, fb.data_ptr(), stream=stream)
-        aov, st_aov = self._render_aov_device(render, want=("position", "normal", "ids"), stream=stream)
+        if demodulate:
+            aov, st_aov = self._render_aov_device(render, want=("position", "normal", "ids", "albedo"), stream=stream, names=AOV_ALL)
+        else:
+            aov, st_aov = self._render_aov_device(render, want=("position", "normal", "ids"), stream=stream)
         if kw.get("sigma_position") is None:
             x0, y0, x1, y1 = region
             pos = aov["position"][y0:y1, x0:x1].reshape(-1, 3)
@@ -183,6 +207,11 @@ class Scene(object):
         if keep_inputs:
             info["beauty"] = fb.cpu().numpy()
             info["aov"] = {name: t.cpu().numpy() for name, t in aov.items()}
+        if demodulate:
+            kw["albedo"] = aov["albedo"]
+            info["albedo_floor"] = kw.setdefault("albedo_floor", ALBEDO_FLOOR)
+        elif "albedo" in kw or "albedo_floor" in kw:
+            raise ValueError("render_denoised takes the albedo from its own AOV pass: demodulate=True")
         out, info["denoise_stats"] = denoise(fb, aov["normal"], aov["position"], aov["ids"], region=region, device=self._device,
                                              stream=stream, out=fb, **kw)
         return out, info
@@ -259,6 +288,9 @@ DENOISE_ITERATIONS = 5
 SIGMA_COLOR = 3.0
 SIGMA_NORMAL = 1.0
 SIGMA_POSITION_FRACTION = 0.1       # of the diagonal of the foreground's bounding box (Scene.render_denoised)
+# the smallest albedo a beauty frame is divided by (fjgpu_denoise_albedo): of the grid in profiles/albedo_pass.txt the floor with the smallest
+# mean squared error on the textured scene
+ALBEDO_FLOOR = 1e-4
 
 
 def _device_tensor(a, name, dtype, channels, dev, shape=None):
@@ -274,13 +306,16 @@ def _device_tensor(a, name, dtype, channels, dev, shape=None):
 
 
 def denoise(color, normal=None, position=None, ids=None, iterations=DENOISE_ITERATIONS, sigma_color=SIGMA_COLOR,
-            sigma_normal=SIGMA_NORMAL, sigma_position=None, stop_at_ids=True, region=None, device=0, stream=None, out=None):
+            sigma_normal=SIGMA_NORMAL, sigma_position=None, stop_at_ids=True, region=None, device=0, stream=None, out=None,
+            albedo=None, albedo_floor=ALBEDO_FLOOR):
     """Edge-avoiding a-trous filter of a beauty frame (include/fjgpu.h: fjgpu_denoise) -> (numpy [H, W, 4] float32, GpuStats).
     color [H, W, 4] RGBA, normal / position [H, W, 3], ids [H, W, 4] int32 (the buffers of Scene.render_aov): numpy arrays, which
     are uploaded, or torch tensors on the device, which are used where they are.  A sigma <= 0 or +inf switches its term off;
     sigma_position is in world units (None: off -- Scene.render_denoised derives one from the scene's size).  region = (xmin, ymin,
     xmax, ymax), None = the frame; pixels outside it are the input's.  out: a float32 device tensor [H, W, 4] to write instead of
-    a new one -- it may be `color` itself (in place) -- whose pixels outside the region are left as they are."""
+    a new one -- it may be `color` itself (in place) -- whose pixels outside the region are left as they are.  albedo [H, W, 3] f32
+    (Scene.render_aov_albedo's "albedo"): the filter runs on colour / max(albedo, albedo_floor) and the result is multiplied by it again
+    (include/fjgpu.h: fjgpu_denoise_albedo); None: no demodulation."""
     import torch
     dev = torch.device("cuda", device)
     c = _device_tensor(color, "color", torch.float32, 4, dev)
@@ -288,6 +323,7 @@ def denoise(color, normal=None, position=None, ids=None, iterations=DENOISE_ITER
     n = _device_tensor(normal, "normal", torch.float32, 3, dev, hw)
     p = _device_tensor(position, "position", torch.float32, 3, dev, hw)
     i = _device_tensor(ids, "ids", torch.int32, 4, dev, hw)
+    a = _device_tensor(albedo, "albedo", torch.float32, 3, dev, hw)
     if out is None:
         out = c.clone()
     elif not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(c.shape)):
@@ -302,7 +338,11 @@ def denoise(color, normal=None, position=None, ids=None, iterations=DENOISE_ITER
     torch.cuda.synchronize(dev)          # uploads and copies ran on torch's stream
     st = ffi.GpuStats()
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    _check(lib().fjgpu_denoise(device, C.byref(d), ptr(c), ptr(n), ptr(p), ptr(i), ptr(out), C.c_void_p(stream or 0), C.byref(st)))
+    if a is not None:
+        _check(lib().fjgpu_denoise_albedo(device, C.byref(d), ptr(c), ptr(n), ptr(p), ptr(i), ptr(a), C.c_float(float(albedo_floor)), ptr(out),
+                                          C.c_void_p(stream or 0), C.byref(st)))
+    else:
+        _check(lib().fjgpu_denoise(device, C.byref(d), ptr(c), ptr(n), ptr(p), ptr(i), ptr(out), C.c_void_p(stream or 0), C.byref(st)))
     return out.cpu().numpy(), st
 
 

@@ -187,6 +187,29 @@ typedef struct fjgpu_aov_buffers {   /* DEVICE pointers, row-major xres*yres, NU
 int fjgpu_render_aov(fjgpu_scene *scene, const fj_render_desc *render, const int32_t *tile_ids, int n_tiles,
     const fjgpu_aov_buffers *buffers, void *hip_stream, fjgpu_stats *stats);
 
+/* fjgpu_render_aov plus an ALBEDO buffer: the surface colour of a pixel without light, what a compositor expects next to depth and
+ * normal and what fjgpu_denoise_albedo divides a beauty frame by.  One camera-ray generation and one closest-hit walk per batch serve
+ * both: `buffers` (may be NULL, or all-NULL) is written as by fjgpu_render_aov, d_albedo (DEVICE [yres][xres][3] f32, may be NULL) gets
+ * the MEAN over the pixel's own rate_x * rate_y samples of the per-sample albedo a, a miss counting 0 (so a silhouette pixel against the
+ * empty background holds coverage x surface, as its beauty value does; a pixel no sample of which hits gets 0 0 0).  Per sample, f32,
+ * every product one multiply, with the statements the shading kernel uses: shader by the slot rule above; tex(i) = the nearest-tap
+ * Texture::Lookup of texture i at the hit's f32 texture coordinates (0, 0 on a curve or a mesh without uv), NO_TEXTURE_COLOR included;
+ * Cd = 1 1 1 on a mesh, the lerp of the piece's end colours on a curve.
+ *   no shader / unknown type   NO_SHADER_COLOR = 0.5 1 0
+ *   ConstantShader             diffuse * tex(texture) where it has one, else diffuse
+ *   PlasticShader              diffuse * tex(diffuse_map), or diffuse
+ *   PathtracingShader          (Cd * tex(diffuse_map)) * diffuse
+ *   HairShader                 Cd * diffuse
+ *   GlassShader                1 1 1
+ * The sum is taken in f64 and divided by the sample count in f64, rounded to f32 once: a pixel whose samples share one albedo holds
+ * exactly that value, any other the f64 mean within one f32 ulp.
+ * Everything else is fjgpu_render_aov's: tiles, region, untouched pixels, batches, transient buffers, stats (resolve_ms covers both
+ * reductions) and the refusals.  FJGPU_EINVAL, the message naming fjgpu_render_aov_albedo, when neither a member of `buffers` nor
+ * d_albedo is set. */
+int fjgpu_render_aov_albedo(fjgpu_scene *scene, const fj_render_desc *render, const int32_t *tile_ids, int n_tiles,
+    const fjgpu_aov_buffers *buffers /* may be NULL */, float *d_albedo /* DEVICE [yres][xres][3], may be NULL */,
+    void *hip_stream, fjgpu_stats *stats);
+
 /* Diagnostics: the camera rays of one tile exactly as fjgpu_render_aov (and the beauty pass) traces them, HOST arrays:
  * rays8 [n][8] = orig xyz, dir xyz, znear, zfar in sample order k = y * nx + x (margin samples included) -- the layout
  * fjgpu_trace takes.  Writes at most `cap` rays (cap 0: none, rays8 may be NULL); returns the tile's sample count n, or a
@@ -194,8 +217,8 @@ int fjgpu_render_aov(fjgpu_scene *scene, const fj_render_desc *render, const int
 int fjgpu_camera_samples(fjgpu_scene *scene, const fj_render_desc *render, int tile_id, double *rays8, int cap);
 
 /* Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010) over a beauty frame, guided by the
- * feature buffers of fjgpu_render_aov.  Device buffers in, device buffers out; no scene handle.  A spatial filter of ONE frame: no albedo
- * demodulation (textured surfaces lean on the colour term), no variance guidance, no temporal reuse.
+ * feature buffers of fjgpu_render_aov.  Device buffers in, device buffers out; no scene handle.  A spatial filter of ONE frame: albedo
+ * demodulation is fjgpu_denoise_albedo below (without it textured surfaces lean on the colour term), no variance guidance, no temporal reuse.
  *
  * All arithmetic is f32 without fused multiply-adds, sums left to right (csrc/device/fjgpu_denoise_math.h is the one source of the
  * kernel, of the host twin the CPU tests run and of the constants).  h = (1/16, 1/4, 3/8, 1/4, 1/16).  For iteration i = 0 ..
@@ -233,6 +256,19 @@ int fjgpu_denoise(int device, const fjgpu_denoise_desc *desc,
                   const int32_t *ids,      /* DEVICE [.][.][4] or NULL (then stop_at_ids = 0)*/
                   float *color_out,        /* DEVICE [.][.][4]; may equal color_in           */
                   void *hip_stream, fjgpu_stats *stats);
+
+/* fjgpu_denoise with albedo demodulation: the filter sees the illumination, not the texture.  albedo NULL: fjgpu_denoise, bit for bit
+ * (albedo_floor is ignored).  Else, for every region pixel and k = r, g, b, in f32:
+ *   a'_k = albedo_k > albedo_floor ? albedo_k : albedo_floor;   D_k = C_k / a'_k  (one IEEE division);
+ *   the filter above runs on (D_r, D_g, D_b, C_alpha), so its colour term compares demodulated values;
+ *   out_k = F_k * a'_k  (one multiply); alpha is the filter's.
+ * `albedo` is a DEVICE [yres][xres][3] f32 buffer (fjgpu_render_aov_albedo's) of which only region pixels are read; color_out may still
+ * equal color_in.  One more pass over the region before the iterations and one after them; the scratch is the same.  stats: gen_ms
+ * includes the demodulating copy, resolve_ms the remodulation.
+ * Errors: those of fjgpu_denoise; FJGPU_EINVAL naming albedo_floor where albedo is set and albedo_floor is not finite and > 0. */
+int fjgpu_denoise_albedo(int device, const fjgpu_denoise_desc *desc, const float *color_in, const float *normal, const float *position,
+    const int32_t *ids, const float *albedo /* DEVICE [yres][xres][3] or NULL */, float albedo_floor, float *color_out,
+    void *hip_stream, fjgpu_stats *stats);
 
 /* Tunables (all have defaults): "batch_tiles" tiles per wavefront batch, "batch_samples" samples per batch where batch_tiles is 0
  * (0, the default: as many as the memory budget holds -- fastest where frames repeat; a caller that renders one frame per scene
