@@ -24,6 +24,7 @@
 #include "fjgpu_denoise.h"
 #include "fjgpu_kernels.h"
 #include "fjgpu_lbvh.h"
+#include "fjgpu_light_cone.h"
 #include "fjgpu_raysort.h"
 #include "fjgpu_tlas.h"
 
@@ -157,6 +158,9 @@ struct fjgpu_scene {
   long aov_batch_samples = 0;      // option "aov_batch_samples": samples per batch of fjgpu_render_aov (0: FJ_AOV_BATCH_SAMPLES)
   long render_calls = 0;           // fjgpu_render_tiles calls that rendered something (the first one sizes its batches for a cold start)
   long count_events;
+  long light_cones = 1;            // option "light_cones" (default 1): the light loop of whole-ray launches settles box misses with the per-light shadow cones built at
+                                   // scene creation (fjgpu_light_cone.h); 0: the instantiation without them, the same pairs through the box test
+  int cone_rows = 0, cone_records = 0;   // queries "light_cone_rows" / "light_cone_records": groups with a row in the table, records of them with a plane
   long count_all_shadow;           // option "count_all_shadow" (default 1): light records of weight zero reach the light loop, which counts their shadow rays as the
                                    // reference does; it never queues them (their colour is exactly zero), so nothing walks them.  0: k_shade drops such records (other counts)
   // queries "stack_peak" / "stack_peak_closest" / "stack_peak_shadow": the most entries any lane's traversal stack held in the launches of the
@@ -774,6 +778,36 @@ static int upload_scene(const fj_scene_desc *desc, fjgpu::HostScene &hs, int dev
   e |= M.upload(dtex.data(), dtex.size(), &S.textures);
   e |= M.upload(hs.light_samples.data(), hs.light_samples.size(), &S.light_samples);
   e |= M.upload(hs.area_lights.data(), hs.area_lights.size(), &S.area_lights);
+  // per-light shadow cones (fjgpu_light_cone.h): one record per (single-instance group, light sample) whose position the light loop uses as it
+  // stands -- point and dome samples; grid and sphere lights draw theirs per shading event.  Lights and instance boxes are fixed for the scene's life.
+  S.light_cones = nullptr; S.cone_rows = nullptr;
+  {
+    const size_t nl = hs.light_samples.size();
+    std::vector<int32_t> rows(hs.groups.size(), -1);
+    std::vector<DLightCone> cones;
+    for (size_t g = 0; g < hs.groups.size() && nl; g++) {
+      if (hs.groups[g].n_instances != 1) continue;
+      const size_t at = cones.size();
+      cones.resize(at + nl);
+      int built = 0;
+      double reach = 1e300;
+      for (size_t l = 0; l < nl; l++) {
+        DLightCone &C = cones[at + l];
+        const DLightSample &LS = hs.light_samples[l];
+        if (LS.type == FJ_POINT_LIGHT || LS.type == FJ_DOME_LIGHT) light_cone_build(LS.P, hs.groups[g].sbounds, &C);
+        else std::memset(&C, 0, sizeof(C));
+        if (C.count > 0) { built++; reach = std::min(reach, C.reach); }
+      }
+      if (!built) { cones.resize(at); continue; }
+      for (size_t l = 0; l < nl; l++) cones[at + l].reach = reach;       // (read once per wave iteration: the row's smallest)
+      rows[g] = (int32_t) (at / nl);
+      sc->cone_rows++; sc->cone_records += built;
+    }
+    if (!cones.empty()) {
+      e |= M.upload(cones.data(), cones.size(), &S.light_cones);
+      e |= M.upload(rows.data(), rows.size(), &S.cone_rows);
+    }
+  }
   S.has_area = hs.area_lights.empty() ? 0 : 1;
   if (e) return fail(FJGPU_ENOMEM, "device allocation / upload failed while creating the scene");
   S.n_light_samples = (int) hs.light_samples.size();
@@ -1035,6 +1069,18 @@ int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value)
   }
   // ... and the node record it reads: the 64-byte quantised twin unless the ribbon test / motion instantiation runs
   if (n == "closest_node_record_bytes") { *value = (double) ((scene->S.has_motion || (scene->S.has_curves && !FJ_CURVE_QNODES) || !FJ_CLOSEST_QNODES) ? sizeof(DNode) : sizeof(DNodeQ)); return 0; }
+  // per-light shadow cones: single-instance groups with a row in the table, records of those rows with at least one plane; and, in a
+  // -DFJ_LIGHT_CONE_VALIDATE build, the light loop's verdicts since the library was loaded and how many of them the exact test contradicted
+  // (every scene of the process; other builds: -1)
+  if (n == "light_cone_rows") { *value = scene->cone_rows; return 0; }
+  if (n == "light_cone_records") { *value = scene->cone_records; return 0; }
+  if (n == "light_cone_verdicts" || n == "light_cone_contradictions") {
+    double v = -1, c = -1;
+    if (hipSetDevice(scene->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(FJGPU_ENODEV, "hipSetDevice / hipDeviceSynchronize");
+    light_cone_validate_counts(&v, &c);
+    *value = n == "light_cone_verdicts" ? v : c;
+    return 0;
+  }
   if (n == "has_curves") { *value = scene->S.has_curves; return 0; }
   if (n == "has_motion") { *value = scene->S.has_motion; return 0; }
   return fail(FJGPU_EINVAL, "unknown query " + n);
@@ -1120,6 +1166,7 @@ int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value)
   if (n == "aov_batch_samples") { scene->aov_batch_samples = value < 0 ? 0 : value; return 0; }
   if (n == "count_nodes") { scene->count_events = value != 0; return 0; }
   if (n == "count_all_shadow") { scene->count_all_shadow = value != 0; return 0; }
+  if (n == "light_cones") { scene->light_cones = value != 0; return 0; }
   if (n == "overlap_shadow") {
     if (value < 0 || value > 2) return fail(FJGPU_EINVAL, "overlap_shadow: 0 off, 1 on, 2 by the batch size");
     scene->overlap = value;
@@ -1461,7 +1508,8 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
   // compact queue records (DShadowRayC) where the consumers rebuild direction and distance: the lean and the curve any-hit walk, point / dome lights, no motion
   S.compact_squeue = scene_compact_squeue(S) ? 1 : 0;
   S.pad_cs_ = 0;
-  swp.compact = S.compact_squeue; swp.pad_ = 0;
+  swp.compact = S.compact_squeue;
+  swp.light_cones = (sc->light_cones && S.light_cones && S.cone_rows) ? 1 : 0;
   swp.queue_capacity = (uint32_t) sc->squeue_cap;
   swp.join_capacity = (swp.pre_resolve && sc->split_shadow && sc->d_join) ? (uint32_t) sc->join_cap : 0u;
   S.shadow_join = swp.join_capacity ? sc->d_join : nullptr;

@@ -66,6 +66,13 @@ __device__ __forceinline__ DLightSample ld_light_sample_k(const DLightSample *p)
   return r;
 }
 
+// the per-light shadow-cone table (fjgpu_light_cone.h) the same way: one double / one int through the scalar cache
+__device__ __forceinline__ double ld_k_f64(const double *p) { return *(const __attribute__((address_space(4))) double *) (uintptr_t) p; }
+__device__ __forceinline__ int32_t ld_k_i32(const int32_t *p) { return *(const __attribute__((address_space(4))) int32_t *) (uintptr_t) p; }
+#ifdef FJ_LIGHT_CONE_VALIDATE
+__device__ unsigned long long g_lightcone[2];      // the light loop's cone verdicts, and how many of them the exact test contradicted
+#endif
+
 #ifndef FJ_CULL_MINB
 #define FJ_CULL_MINB 1
 #endif
@@ -85,7 +92,10 @@ __device__ __forceinline__ DLightSample ld_light_sample_k(const DLightSample *p)
 #ifndef FJ_CULL_LDS_NODES
 #define FJ_CULL_LDS_NODES 292      // 16 352 bytes
 #endif
-template <bool kHair, bool kArea, bool kSplit, bool kNodesLds = false>
+// kCone (whole rays, point / dome lights, no hair; ShadowParams.light_cones): a wave iteration whose records share ONE single-instance group with a
+// row in the cone table settles the box misses of its (point, light) pairs with the light's precomputed shadow cone (fjgpu_light_cone.h) -- a few
+// dot products of Ln with wave-uniform normals -- and runs the reciprocals and the six-plane box test for the undecided lanes only, if any.
+template <bool kHair, bool kArea, bool kSplit, bool kNodesLds = false, bool kCone = false>
 __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSplit ? FJ_CULL_MINB_PLAIN : FJ_CULL_MINB_WHOLE)) k_shadow_cull(DScene S, ShadowParams sp, const DLightRec *lrecs,
     uint32_t rec_begin, uint32_t rec_end, float *s_accum, DShadowRay *squeue, DCounters *cnt, int count_events)
 {
@@ -164,6 +174,23 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
     // entered it at t <= 0 < distance, which is all BoxRayIntersect asks for (src/fj_box.cc:73-138).
     const bool deep_inside = active && g_single &&
         Ps.x > sb[0] + 2e-4 && Ps.x < sb[3] - 2e-4 && Ps.y > sb[1] + 2e-4 && Ps.y < sb[4] - 2e-4 && Ps.z > sb[2] + 2e-4 && Ps.z < sb[5] - 2e-4;
+    // The cone row of the iteration (wave-uniform; null: today's path for every pair) and the lanes whose point lies within the row's reach.
+    // Lane 0 is active in every iteration.
+    const DLightCone *cone_row = nullptr;
+    bool cone_lane = false;
+    if (kCone) {
+      static_assert(!kCone || (!kHair && !kArea && !kSplit), "the cones serve whole rays to fixed light positions");
+      const int grp = active ? R.group : -1;
+      const int g0 = __builtin_amdgcn_readfirstlane(grp);
+      if (__ballot(active && grp != g0) == 0ull) {
+        const int row = ld_k_i32(S.cone_rows + g0);
+        if (row >= 0) {
+          cone_row = S.light_cones + (size_t) row * nl;
+          const double reach = ld_k_f64(&cone_row->reach);
+          cone_lane = active && !deep_inside && fmax(fmax(fabs(Ps.x), fabs(Ps.y)), fabs(Ps.z)) <= reach;
+        }
+      }
+    }
     // (Tried in round 3 and dropped: per-lane LISTS of the lights that are not surely behind the surface -- a cheap first
     // pass with the light index wave-uniform, then every lane walks its own list, so that the expensive part runs
     // max-list-length times instead of once per light.  Only 36 % of C3's pairs are lit, yet the loop got slower, 22.8 ->
@@ -184,6 +211,9 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
       bool plain_s = false;
       double dist_s = 0;
       float k_s[3] = {0.f, 0.f, 0.f};
+      // (the plane count of the light's cone comes with the sample; its normals -- 36 SGPRs -- are read where they are used, four planes at a time)
+      int lc_count = 0;
+      if (kCone && cone_row) lc_count = ld_k_i32(&cone_row[l].count);
       if (active) {
         // (the table is written once at scene creation: read through the constant address space the wave-uniform record comes through the scalar
         // cache into SGPRs -- as a generic pointer it was three vector loads of 64 identical lanes, waited for at the head of every iteration:
@@ -277,8 +307,36 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
           bool maybe_occluded = false;
           if (sp.cast_shadow) {
             r_shadow++;
-            // group bounds test + leaf bounds of the instance BVH, as culling
-            const bool test = carries && !has_negative_zero(Ln);
+            // the light's shadow cone: a point outside one of its planes surely misses the group's box (one-sided contract of fjgpu_light_cone.h;
+            // a direction with a zero component and a point beyond the row's reach are not put to it).  The event counted is the parent's: a
+            // candidate instance whose box the ray misses.
+            bool sure = false;
+            if (kCone && lc_count > 0) {
+              const bool cand = cone_lane && carries && plain_dir(Ln);
+              if (__ballot(cand)) {
+                // Four planes per trip to the scalar cache: one wait for twelve operands, not one per plane.  The build function put the planes
+                // in an order in which the first four settle nearly every pair (all of them where the cone has four sides); planes not in use are zero.
+                const double *pn = &cone_row[l].n[0][0];
+                const double m = light_cone_margin(Ln.x, Ln.y, Ln.z);
+#define FJ_LC_PLANE(j) (cand & light_cone_plane_out(ld_k_f64(pn + 3 * (j)), ld_k_f64(pn + 3 * (j) + 1), ld_k_f64(pn + 3 * (j) + 2), Ln.x, Ln.y, Ln.z, m))
+                sure = FJ_LC_PLANE(0) | FJ_LC_PLANE(1) | FJ_LC_PLANE(2) | FJ_LC_PLANE(3);
+                if (lc_count > 4 && __ballot(cand && !sure) != 0ull) sure = sure | FJ_LC_PLANE(4) | FJ_LC_PLANE(5);      // some candidate of the wave is still undecided
+#undef FJ_LC_PLANE
+              }
+#ifdef FJ_LIGHT_CONE_VALIDATE
+              {
+                // debug build: the exact test behind every verdict
+                const bool wrong = sure && box_ray_ref(sb, Ps, Ln, .0001, distance);
+                const unsigned long long mv = __ballot(sure), mw = __ballot(wrong);
+                if (mv && lane == (unsigned) __builtin_ctzll(mv)) { atomicAdd(&g_lightcone[0], (unsigned long long) __popcll(mv)); if (mw) atomicAdd(&g_lightcone[1], (unsigned long long) __popcll(mw)); }
+              }
+#endif
+              if (sure) r_insts++;
+            }
+            // group bounds test + leaf bounds of the instance BVH, as culling (with cones: for the lanes they left undecided, if the wave has any)
+            const bool need = carries && !(kCone && sure);
+            bool test = false;
+            if (!kCone || __ballot(need)) test = need && !has_negative_zero(Ln);
             if (deep_inside) maybe_occluded = test;
             else if (test) {
               const V3 winv = mk(filter_rcp(Ln.x), filter_rcp(Ln.y), filter_rcp(Ln.z));

@@ -65,7 +65,8 @@ struct ShadowParams {
   uint32_t join_capacity;      // slots of DScene.shadow_join (0: shadow rays into groups of several instances stay whole)
   int32_t cast_shadow;
   int32_t compact;             // 1: the queue holds DShadowRayC records (DScene.compact_squeue)
-  int32_t pad_;
+  int32_t light_cones;         // 1: whole-ray launches of scenes with a cone table (DScene.light_cones) settle box misses with the per-light cones
+                               // (scene option "light_cones", default 1); 0: the instantiation without them
 };
 
 struct ResolveParams {
@@ -90,6 +91,9 @@ int launch_quantize_nodes(hipStream_t st, const DNode *nodes, uint32_t n, const 
 // tile_px pixels per tile, or scatter such a slab into the framebuffer (unpack)
 int launch_move_tiles(hipStream_t st, bool unpack, float *fb, int xres, const int32_t *d_rects, int n_tiles, int tile_px, float *slab);
 void set_anyhit_filter_off(long v);     // diagnostics: fjgpu_global_option("anyhit_filter_off")
+// -DFJ_LIGHT_CONE_VALIDATE builds: the cone verdicts of the light loop so far (current device) and how many of them the exact test contradicted;
+// other builds: -1, -1
+void light_cone_validate_counts(double *verdicts, double *contradictions);
 void debug_phase_stats();     // FJ_PHASE_STATS builds: print and reset the any-hit walk's phase tallies (stderr)
 // threads of the largest persistent grid (sizes per-thread scratch such as the stack overflow area)
 size_t persistent_threads();

@@ -33,6 +33,7 @@
 
 #include "fjgpu_dev_math.h"
 #include "fjgpu_tri_filter.h"
+#include "fjgpu_light_cone.h"
 #include "fjgpu_dev_curve.h"
 #include "fjgpu_dev_traverse.h"
 #include "fjgpu_dev_flat.h"
@@ -382,7 +383,10 @@ int launch_shadow_cull(hipStream_t st, const DScene &S, const ShadowParams &sp, 
     if (split) hipLaunchKernelGGL((k_shadow_cull<false, false, true, true>), dim3(persistent_grid((threads + BLOCK - 1) / BLOCK, cull_blocks_per_cu(blocks_per_cu))), dim3(BLOCK), 0, st, S, sp, lrecs, b, e, s_accum, squeue, cnt, count_events);
     else hipLaunchKernelGGL((k_shadow_cull<false, false, false, true>), dim3(persistent_grid((threads + BLOCK - 1) / BLOCK, cull_blocks_per_cu(blocks_per_cu))), dim3(BLOCK), 0, st, S, sp, lrecs, b, e, s_accum, squeue, cnt, count_events);
   }
-  else { if (split) FJ_LAUNCH_CULL(false, false, true); else FJ_LAUNCH_CULL(false, false, false); }
+  else if (split) FJ_LAUNCH_CULL(false, false, true);
+  else if (sp.light_cones && S.light_cones && S.cone_rows)      // whole rays, a cone table: box misses settled by the per-light shadow cones
+    hipLaunchKernelGGL((k_shadow_cull<false, false, false, false, true>), dim3(persistent_grid((threads + BLOCK - 1) / BLOCK, cull_blocks_per_cu(blocks_per_cu))), dim3(BLOCK), 0, st, S, sp, lrecs, b, e, s_accum, squeue, cnt, count_events);
+  else FJ_LAUNCH_CULL(false, false, false);
 #undef FJ_LAUNCH_CULL
   LAUNCH_CHECK();
   return 0;
@@ -449,6 +453,15 @@ int launch_move_tiles(hipStream_t st, bool unpack, float *fb, int xres, const in
     LAUNCH_CHECK();
   }
   return 0;
+}
+
+void light_cone_validate_counts(double *verdicts, double *contradictions)
+{
+  *verdicts = -1; *contradictions = -1;
+#ifdef FJ_LIGHT_CONE_VALIDATE
+  unsigned long long c[2];
+  if (hipMemcpyFromSymbol(c, HIP_SYMBOL(g_lightcone), sizeof(c)) == hipSuccess) { *verdicts = (double) c[0]; *contradictions = (double) c[1]; }
+#endif
 }
 
 void debug_phase_stats()

@@ -253,6 +253,7 @@ struct DAreaLight {
 };
 
 struct DLightHair;
+struct DLightCone;             // fjgpu_light_cone.h
 
 struct DScene {
   const DPrimSet *primsets;
@@ -265,6 +266,11 @@ struct DScene {
   const fj_shader_desc *shaders;
   const DTexture *textures;
   const DLightSample *light_samples;
+  // per-light shadow cones (fjgpu_light_cone.h), built once at scene creation: row r holds one record per light sample, cone_rows[g] is the row
+  // of single-instance group g or -1 (groups of several instances; groups none of whose lights has a cone).  Both null: no group has a row.
+  // (The row index is a table of its own and not a DGroup member: the walks copy DGroups verbatim into a fixed LDS budget of 64 bytes each.)
+  const DLightCone *light_cones;
+  const int32_t *cone_rows;    // [n_groups]
   DLightHair *lrec_hair;       // work buffer (set per render call) or null
   uint32_t shadow_queue_cap;   // entries of the shadow-ray queue (a walk never reads past it, whatever the slot counter says)
   uint32_t cam_slot0;          // implicit camera rays: sample slot of ray 0 of the launch (a level walked in chunks)

@@ -275,7 +275,9 @@ int fjgpu_denoise_albedo(int device, const fjgpu_denoise_desc *desc, const float
  * sets a few M: the work arena shrinks from ~110 GB to a few GB at the headline size and the cold frame starts sooner),
  * "count_nodes" 0/1 enable traversal event counters, "overlap_shadow" 0/1 run the shadow work of
  * a recursion level on its own stream, concurrent with the next level; "release_work" 1: hand the work arena back to the driver
- * now (the scene stays resident; the next render call allocates again). Returns 0 or FJGPU_EINVAL. */
+ * now (the scene stays resident; the next render call allocates again); "light_cones" 1/0 (default 1): the light loop settles the box misses
+ * of single-instance shadow groups with the per-light shadow cones built at scene creation (point lights, whole rays; same results, fewer
+ * instructions); 0: every pair takes the box test. Returns 0 or FJGPU_EINVAL. */
 int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value);
 
 /* Process-wide options read by fjgpu_scene_create (which stands for the reference's
@@ -353,7 +355,10 @@ int fjgpu_host_instance_level(const fj_scene_desc *desc, int group, int32_t *out
  * largest call so far sized it; scene_bytes + work_bytes = the HBM this scene holds), "stack_peak" (with option count_nodes on: the most
  * entries any lane's traversal stack held in the launches of the last render_* / trace call -- "stack_peak_closest" / "stack_peak_shadow": of the
  * closest-hit / the shadow walks alone; 0 without the option), "stack_lds" / "stack_lds_anyhit" / "stack_lds_curves" / "stack_lds_min" (entries
- * the walks keep in LDS: a peak above a walk's figure went through the global overflow area).  Returns 0 or FJGPU_EINVAL. */
+ * the walks keep in LDS: a peak above a walk's figure went through the global overflow area), "light_cone_rows" / "light_cone_records" (single-instance
+ * groups with a row in the shadow-cone table; records of those rows that hold a cone), "light_cone_verdicts" / "light_cone_contradictions" (a
+ * -DFJ_LIGHT_CONE_VALIDATE build: cone verdicts of the light loop since the library was loaded, and how many the exact box test contradicted;
+ * -1 in any other build).  Returns 0 or FJGPU_EINVAL. */
 int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value);
 
 /* Diagnostics: the host-side math that feeds geometry to the device (matrices,
