@@ -22,6 +22,7 @@
 #include "fjgpu.h"
 #include "fjgpu_build.h"
 #include "fjgpu_denoise.h"
+#include "fjgpu_denoise_variance.h"
 #include "fjgpu_kernels.h"
 #include "fjgpu_lbvh.h"
 #include "fjgpu_light_cone.h"
@@ -2368,6 +2369,157 @@ int fjgpu_denoise(int device, const fjgpu_denoise_desc *d, const float *color_in
     const int32_t *ids, float *color_out, void *hip_stream, fjgpu_stats *stats)
 {
   return fjgpu_denoise_albedo(device, d, color_in, normal, position, ids, nullptr, 0.f, color_out, hip_stream, stats);
+}
+
+// ---- variance-guided denoiser (fjgpu_denoise_variance.hip, fjgpu_denoise_var_math.h).  fjgpu_denoise's shape and scratch, plus two f32
+// planes of the region: the estimate (or nothing, where the caller brings a variance) lands in one, the iterations ping-pong between them.
+namespace {
+
+// the refusals both entry points share, each naming `fn`; 0 or the error
+int dnv_check(const char *fn, const fjgpu_denoise_desc *d, const float *color, bool with_iterations)
+{
+  const std::string f(fn);
+  if (d->xres <= 0 || d->yres <= 0) return fail(FJGPU_EINVAL, f + ": resolution must be positive");
+  if (d->region[0] < 0 || d->region[1] < 0 || d->region[2] > d->xres || d->region[3] > d->yres ||
+      d->region[0] >= d->region[2] || d->region[1] >= d->region[3])
+    return fail(FJGPU_EINVAL, f + ": region must be a non-empty rectangle inside the frame");
+  if (with_iterations && (d->iterations < 1 || d->iterations > FJ_DN_MAX_ITERATIONS)) return fail(FJGPU_EINVAL, f + ": iterations must be 1..8");
+  if (std::isnan(d->sigma_color) || std::isnan(d->sigma_normal) || std::isnan(d->sigma_position)) return fail(FJGPU_EINVAL, f + ": a sigma is NaN");
+  if ((uintptr_t) color & 15u) return fail(FJGPU_EINVAL, f + ": colour buffers must be 16-byte aligned");
+  if (d->region[3] - d->region[1] > 65535 * 4) return fail(FJGPU_EINVAL, f + ": a region of more than 262140 rows");
+  return 0;
+}
+
+}  // namespace
+
+int fjgpu_denoise_estimate_variance(int device, const fjgpu_denoise_desc *d, const float *color, const float *normal, const float *position,
+    const int32_t *ids, float *variance_out, void *hip_stream, fjgpu_stats *stats)
+{
+  const char *fn = "fjgpu_denoise_estimate_variance";
+  if (!d || !color || !variance_out)
+    return fail(FJGPU_EINVAL, std::string(fn) + ": null argument (desc, color and variance_out are required)");
+  if (const int e = dnv_check(fn, d, color, false)) return e;
+  if ((const void *) variance_out == (const void *) color) return fail(FJGPU_EINVAL, std::string(fn) + ": variance_out must not be the colour buffer");
+  if (fjgpu_device_count() < 1) return fail(FJGPU_ENODEV, std::string(fn) + ": no HIP device is visible");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const int w = d->region[2] - d->region[0], h = d->region[3] - d->region[1];
+  const size_t npx = (size_t) w * (size_t) h;
+  const int stop = (d->stop_at_ids && ids) ? 1 : 0;
+  DeviceBuffers W;
+  float *d_guide;
+  if (W.alloc(npx * 8, &d_guide)) return fail(FJGPU_ENOMEM, std::string(fn) + ": device allocation failed");
+  fjgpu_stats acc;
+  std::memset(&acc, 0, sizeof(acc));
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int rc = 0;
+  for (int k = 0; k < 2 && !rc; k++) if (hipEventCreate(&ev[k]) != hipSuccess) rc = -1;
+  const size_t origin = (size_t) d->region[1] * (size_t) d->xres + (size_t) d->region[0];
+  if (!rc) {
+    (void) hipEventRecord(ev[0], st);
+    rc = launch_dn_pack_var(st, color + origin * 4, d->xres, normal, position, ids, d->xres, d->region[0], d->region[1], w, h, d_guide);
+    if (!rc) rc = launch_dn_variance(st, d_guide, variance_out + origin, d->xres, w, h, stop,
+                                     fj_dn_constants(0.f, normal ? d->sigma_normal : 0.f, position ? d->sigma_position : 0.f, 0));
+    (void) hipEventRecord(ev[1], st);
+  }
+  const hipError_t se = hipStreamSynchronize(st);      // (also before the transient buffer goes away)
+  if (rc == 0 && se == hipSuccess) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) acc.gen_ms = acc.total_ms = ms;
+  }
+  for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
+  if (rc) return fail(FJGPU_ENODEV, std::string(fn) + ": HIP failure: " + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
+  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string(fn) + ": stream synchronize: " + hipGetErrorString(se));
+  if (stats) *stats = acc;
+  return 0;
+}
+
+int fjgpu_denoise_variance(int device, const fjgpu_denoise_desc *d, float sigma_luminance, const float *color_in, const float *normal,
+    const float *position, const int32_t *ids, const float *albedo, float albedo_floor, const float *variance_in, float *color_out,
+    float *variance_out, void *hip_stream, fjgpu_stats *stats)
+{
+  const char *fn = "fjgpu_denoise_variance";
+  if (albedo && !(std::isfinite(albedo_floor) && albedo_floor > 0))
+    return fail(FJGPU_EINVAL, std::string(fn) + ": albedo_floor must be finite and > 0");
+  if (!d || !color_in || !color_out)
+    return fail(FJGPU_EINVAL, std::string(fn) + ": null argument (desc, color_in and color_out are required)");
+  if (const int e = dnv_check(fn, d, (const float *) ((uintptr_t) color_in | (uintptr_t) color_out), true)) return e;
+  if (std::isnan(sigma_luminance)) return fail(FJGPU_EINVAL, std::string(fn) + ": sigma_luminance is NaN");
+  if (variance_out && ((const void *) variance_out == (const void *) variance_in || (const void *) variance_out == (const void *) color_in ||
+                       (const void *) variance_out == (const void *) color_out))
+    return fail(FJGPU_EINVAL, std::string(fn) + ": variance_out must not be variance_in or a colour buffer");
+  if (variance_in && ((const void *) variance_in == (const void *) color_out))
+    return fail(FJGPU_EINVAL, std::string(fn) + ": variance_in must not be color_out");
+  if (fjgpu_device_count() < 1) return fail(FJGPU_ENODEV, std::string(fn) + ": no HIP device is visible");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const int w = d->region[2] - d->region[0], h = d->region[3] - d->region[1];
+  const size_t npx = (size_t) w * (size_t) h;
+  const int n_it = d->iterations;
+  const int stop = (d->stop_at_ids && ids) ? 1 : 0;
+  const DnConst k = fj_dn_constants(0.f, normal ? d->sigma_normal : 0.f, position ? d->sigma_position : 0.f, 0);
+
+  DeviceBuffers W;
+  float *d_frame[2], *d_guide, *d_var[2];
+  if (W.alloc(npx * 4, &d_frame[0]) || W.alloc(npx * 4, &d_frame[1]) || W.alloc(npx * 8, &d_guide) || W.alloc(npx, &d_var[0]) ||
+      W.alloc(npx, &d_var[1]))
+    return fail(FJGPU_ENOMEM, std::string(fn) + ": device allocation failed");
+
+  fjgpu_stats acc;
+  std::memset(&acc, 0, sizeof(acc));
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};      // call start, pack / demodulation / estimate done, iterations done
+  int rc = 0;
+  for (int e = 0; e < 3 && !rc; e++) if (hipEventCreate(&ev[e]) != hipSuccess) rc = -1;
+  const size_t origin = (size_t) d->region[1] * (size_t) d->xres + (size_t) d->region[0];
+  const float *src = color_in + origin * 4;
+  int src_stride = d->xres;
+  if (!rc) (void) hipEventRecord(ev[0], st);
+  if (!rc && albedo) {
+    // the filter's input is colour / albedo, staged in the scratch frame iteration 0 does not write (iteration 1 is the first to)
+    rc = launch_dn_demodulate(st, src, d->xres, albedo, d->xres, d->region[0], d->region[1], albedo_floor, d_frame[1], w, w, h);
+    src = d_frame[1]; src_stride = w;
+  } else if (!rc && n_it == 1 && color_in == color_out) {
+    // in place with a single iteration: that launch would read pixels other blocks have written
+    if (hipMemcpy2DAsync(d_frame[1], (size_t) w * 16, src, (size_t) d->xres * 16, (size_t) w * 16, (size_t) h, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = -1;
+    src = d_frame[1]; src_stride = w;
+  }
+  const float *vin = variance_in ? variance_in + origin : d_var[0];
+  int vin_stride = variance_in ? d->xres : w;
+  if (!rc && variance_in) {
+    rc = launch_dn_pack(st, normal, position, ids, d->xres, d->region[0], d->region[1], w, h, d_guide);
+  } else if (!rc) {
+    // the estimate is of the frame the iterations filter: the demodulated one where there is an albedo
+    rc = launch_dn_pack_var(st, src, src_stride, normal, position, ids, d->xres, d->region[0], d->region[1], w, h, d_guide);
+    if (!rc) rc = launch_dn_variance(st, d_guide, d_var[0], w, w, h, stop, k);
+  }
+  if (ev[1]) (void) hipEventRecord(ev[1], st);
+  for (int i = 0; i < n_it && !rc; i++) {
+    const bool last = i == n_it - 1;
+    float *dst = last ? color_out + origin * 4 : d_frame[i & 1];
+    const int dst_stride = last ? d->xres : w;
+    // iteration i reads d_var[i & 1] (iteration 0: that or the caller's plane) and writes the other
+    float *vout = (last && variance_out) ? variance_out + origin : d_var[(i + 1) & 1];
+    const int vout_stride = (last && variance_out) ? d->xres : w;
+    rc = launch_dn_atrous_var(st, src, src_stride, d_guide, vin, vin_stride, dst, dst_stride, vout, vout_stride, w, h, 1 << i, stop,
+                              sigma_luminance, k);
+    src = dst; src_stride = dst_stride;
+    vin = vout; vin_stride = vout_stride;
+  }
+  if (!rc && albedo) rc = launch_dn_remodulate(st, color_out + origin * 4, d->xres, albedo, d->xres, d->region[0], d->region[1], albedo_floor, w, h);
+  if (ev[2]) (void) hipEventRecord(ev[2], st);
+  const hipError_t se = hipStreamSynchronize(st);      // (also before the transient buffers go away)
+  if (rc == 0 && se == hipSuccess) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) acc.gen_ms = ms;
+    if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) acc.resolve_ms = ms;
+    if (hipEventElapsedTime(&ms, ev[0], ev[2]) == hipSuccess) acc.total_ms = ms;
+    acc.batches = (uint32_t) n_it;
+  }
+  for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
+  if (rc) return fail(FJGPU_ENODEV, std::string(fn) + ": HIP failure: " + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
+  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string(fn) + ": stream synchronize: " + hipGetErrorString(se));
+  if (stats) *stats = acc;
+  return 0;
 }
 
 int fjgpu_camera_samples(fjgpu_scene *sc, const fj_render_desc *r, int tile_id, double *rays8, int cap)

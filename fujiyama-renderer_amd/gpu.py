@@ -41,6 +41,10 @@ def lib():
                                            C.c_float, C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
         L.fjgpu_denoise.argtypes = [C.c_int, C.POINTER(ffi.DenoiseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.POINTER(ffi.GpuStats)]
+        L.fjgpu_denoise_estimate_variance.argtypes = [C.c_int, C.POINTER(ffi.DenoiseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
+        L.fjgpu_denoise_variance.argtypes = [C.c_int, C.POINTER(ffi.DenoiseDesc), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
         L.fjgpu_camera_samples.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_int, C.c_void_p, C.c_int]
         L.fjgpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.fjgpu_global_option.argtypes = [C.c_char_p, C.c_long]
@@ -171,7 +175,7 @@ class Scene(object):
             _check(lib().fjgpu_render_aov(self._h, C.byref(render), ids_p, n, C.byref(bufs), C.c_void_p(stream or 0), C.byref(st)))
         return tensors, st
 
-    def render_denoised(self, render, keep_inputs=False, stream=None, demodulate=False, **kw):
+    def render_denoised(self, render, keep_inputs=False, stream=None, demodulate=False, variance_guided=False, **kw):
         """A beauty frame, its feature buffers and the denoiser (include/fjgpu.h: fjgpu_denoise) in one go, everything on the device:
         render_tiles into a device framebuffer, render_aov(want=("position", "normal", "ids")), denoise over the render region; the
         only copy to the host is the result's.  -> (numpy [H, W, 4] float32, info) with info["beauty_stats"], info["aov_stats"],
@@ -181,7 +185,10 @@ class Scene(object):
         of the region; a frame without foreground switches the term off.  The AOV pass's refusals (adaptive sampler, time-sampled
         camera, scene with motion) pass through unchanged.  demodulate=True adds "albedo" to the one AOV call (render_aov_albedo's) and filters the
         frame divided by it (fjgpu_denoise_albedo: textures are kept out of the filter); info["aov"] then holds the albedo too and
-        info["albedo_floor"] is the value used (denoise()'s albedo_floor)."""
+        info["albedo_floor"] is the value used (denoise()'s albedo_floor).  variance_guided=True filters with denoise_variance()
+        (include/fjgpu.h: fjgpu_denoise_variance, the variance estimated from the frame; `kw` are then its parameters) in place of
+        denoise(); it combines with demodulate, and the derived sigma_position is SIGMA_POSITION_FRACTION_VARIANCE of the diagonal.  info["sigma_luminance"] is the value used and, with keep_inputs, info["variance"] the
+        [H, W] variance of the last iteration."""
         import torch
         dev = torch.device("cuda", self._device)
         region = tuple(int(v) for v in render.region)
@@ -200,7 +207,8 @@ class Scene(object):
             keep = (aov["ids"][y0:y1, x0:x1, 0].reshape(-1) >= 0) & torch.isfinite(pos).all(dim=1)
             if bool(keep.any()):
                 p = pos[keep].double()
-                kw["sigma_position"] = SIGMA_POSITION_FRACTION * float(torch.linalg.norm(p.max(dim=0).values - p.min(dim=0).values))
+                fraction = SIGMA_POSITION_FRACTION_VARIANCE if variance_guided else SIGMA_POSITION_FRACTION
+                kw["sigma_position"] = fraction * float(torch.linalg.norm(p.max(dim=0).values - p.min(dim=0).values))
             else:
                 kw["sigma_position"] = 0.0
         info = dict(beauty_stats=st_beauty, aov_stats=st_aov, sigma_position=kw["sigma_position"])
@@ -212,6 +220,16 @@ class Scene(object):
             info["albedo_floor"] = kw.setdefault("albedo_floor", ALBEDO_FLOOR)
         elif "albedo" in kw or "albedo_floor" in kw:
             raise ValueError("render_denoised takes the albedo from its own AOV pass: demodulate=True")
+        if variance_guided:
+            info["sigma_luminance"] = kw.setdefault("sigma_luminance", SIGMA_LUMINANCE)
+            if "variance" in kw or "return_variance" in kw or "variance_out" in kw:
+                raise ValueError("render_denoised estimates the variance from its own frame")
+            res = denoise_variance(fb, aov["normal"], aov["position"], aov["ids"], region=region, device=self._device, stream=stream,
+                                   out=fb, return_variance=bool(keep_inputs), **kw)
+            if keep_inputs:
+                info["variance"] = res[1]
+            info["denoise_stats"] = res[-1]
+            return res[0], info
         out, info["denoise_stats"] = denoise(fb, aov["normal"], aov["position"], aov["ids"], region=region, device=self._device,
                                              stream=stream, out=fb, **kw)
         return out, info
@@ -343,6 +361,98 @@ def denoise(color, normal=None, position=None, ids=None, iterations=DENOISE_ITER
                                           C.c_void_p(stream or 0), C.byref(st)))
     else:
         _check(lib().fjgpu_denoise(device, C.byref(d), ptr(c), ptr(n), ptr(p), ptr(i), ptr(out), C.c_void_p(stream or 0), C.byref(st)))
+    return out.cpu().numpy(), st
+
+
+# the luminance sigma of denoise_variance(), in units of the local standard deviation: of the grid in profiles/denoise_variance.txt (the frames
+# and the method of the grid above, scripts/denoise_variance_grid.py) the setting with the smallest mean squared error: sigma_luminance 4,
+# sigma_normal 1, sigma_position 0.03 of the diagonal.  The position term is tighter than the plain filter's: the estimate's 7 x 7 window
+# must not straddle an illumination edge, which it would take for variance.
+SIGMA_LUMINANCE = 4.0
+SIGMA_POSITION_FRACTION_VARIANCE = 0.03       # of the diagonal of the foreground's bounding box (Scene.render_denoised(variance_guided=True))
+
+
+def _variance_tensor(v, name, dev, hw):
+    import torch
+    if v is None:
+        return None
+    t = v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))
+    t = t.to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(t.shape) != tuple(hw):
+        raise ValueError("%s must be [H, W] = %d, %d, not %s" % ((name,) + tuple(hw) + (tuple(t.shape),)))
+    return t
+
+
+def _denoise_desc(hw, region, iterations, sigma_normal, sigma_position, stop_at_ids):
+    d = ffi.DenoiseDesc()
+    d.yres, d.xres = hw
+    d.region[:] = (0, 0, d.xres, d.yres) if region is None else tuple(int(v) for v in region)
+    d.iterations = int(iterations)
+    d.sigma_color, d.sigma_normal = 0.0, float(sigma_normal)
+    d.sigma_position = 0.0 if sigma_position is None else float(sigma_position)
+    d.stop_at_ids = 1 if stop_at_ids else 0
+    return d
+
+
+def estimate_variance(color, normal=None, position=None, ids=None, region=None, sigma_normal=SIGMA_NORMAL, sigma_position=None,
+                      stop_at_ids=True, device=0, stream=None):
+    """Spatial variance estimate of a beauty frame's luminance under the AOV guides (include/fjgpu.h: fjgpu_denoise_estimate_variance)
+    -> (numpy [H, W] float32, GpuStats).  The inputs and the sigmas are denoise()'s; pixels outside the region are 0."""
+    import torch
+    dev = torch.device("cuda", device)
+    c = _device_tensor(color, "color", torch.float32, 4, dev)
+    hw = tuple(c.shape[:2])
+    n = _device_tensor(normal, "normal", torch.float32, 3, dev, hw)
+    p = _device_tensor(position, "position", torch.float32, 3, dev, hw)
+    i = _device_tensor(ids, "ids", torch.int32, 4, dev, hw)
+    var = torch.zeros(hw, dtype=torch.float32, device=dev)
+    d = _denoise_desc(hw, region, 1, sigma_normal, sigma_position, stop_at_ids)
+    torch.cuda.synchronize(dev)          # uploads and the fill ran on torch's stream
+    st = ffi.GpuStats()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _check(lib().fjgpu_denoise_estimate_variance(device, C.byref(d), ptr(c), ptr(n), ptr(p), ptr(i), ptr(var), C.c_void_p(stream or 0),
+                                                 C.byref(st)))
+    return var.cpu().numpy(), st
+
+
+def denoise_variance(color, normal=None, position=None, ids=None, albedo=None, variance=None, sigma_luminance=SIGMA_LUMINANCE,
+                     iterations=DENOISE_ITERATIONS, sigma_normal=SIGMA_NORMAL, sigma_position=None, stop_at_ids=True, region=None,
+                     device=0, stream=None, out=None, albedo_floor=ALBEDO_FLOOR, return_variance=False, variance_out=None):
+    """Variance-guided a-trous filter of a beauty frame (include/fjgpu.h: fjgpu_denoise_variance) -> (numpy [H, W, 4] float32, GpuStats),
+    or with return_variance (numpy [H, W, 4], numpy [H, W] variance of the last iteration, GpuStats).  The inputs, region, out, albedo
+    and albedo_floor are denoise()'s; there is no colour sigma: sigma_luminance is in units of the local standard deviation (<= 0 or
+    +inf: off).  variance [H, W] f32 (numpy or device tensor, finite and >= 0): the variance of the frame's luminance -- of the
+    demodulated frame's where there is an albedo; None: estimated as estimate_variance() does.  variance_out: a float32 device tensor
+    [H, W] to take the last iteration's variance (implies return_variance); its pixels outside the region are left as they are."""
+    import torch
+    dev = torch.device("cuda", device)
+    c = _device_tensor(color, "color", torch.float32, 4, dev)
+    hw = tuple(c.shape[:2])
+    n = _device_tensor(normal, "normal", torch.float32, 3, dev, hw)
+    p = _device_tensor(position, "position", torch.float32, 3, dev, hw)
+    i = _device_tensor(ids, "ids", torch.int32, 4, dev, hw)
+    a = _device_tensor(albedo, "albedo", torch.float32, 3, dev, hw)
+    v = _variance_tensor(variance, "variance", dev, hw)
+    if out is None:
+        out = c.clone()
+    elif not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(c.shape)):
+        raise ValueError("out must be a contiguous float32 tensor of color's shape on the device")
+    if variance_out is not None:
+        if not (torch.is_tensor(variance_out) and variance_out.device == dev and variance_out.dtype == torch.float32 and
+                variance_out.is_contiguous() and tuple(variance_out.shape) == hw):
+            raise ValueError("variance_out must be a contiguous float32 tensor [H, W] on the device")
+        return_variance = True
+    elif return_variance:
+        variance_out = torch.zeros(hw, dtype=torch.float32, device=dev)
+    d = _denoise_desc(hw, region, iterations, sigma_normal, sigma_position, stop_at_ids)
+    torch.cuda.synchronize(dev)          # uploads and copies ran on torch's stream
+    st = ffi.GpuStats()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _check(lib().fjgpu_denoise_variance(device, C.byref(d), C.c_float(float(sigma_luminance)), ptr(c), ptr(n), ptr(p), ptr(i), ptr(a),
+                                        C.c_float(float(albedo_floor)), ptr(v), ptr(out), ptr(variance_out), C.c_void_p(stream or 0),
+                                        C.byref(st)))
+    if return_variance:
+        return out.cpu().numpy(), variance_out.cpu().numpy(), st
     return out.cpu().numpy(), st
 
 

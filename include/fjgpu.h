@@ -218,7 +218,7 @@ int fjgpu_camera_samples(fjgpu_scene *scene, const fj_render_desc *render, int t
 
 /* Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010) over a beauty frame, guided by the
  * feature buffers of fjgpu_render_aov.  Device buffers in, device buffers out; no scene handle.  A spatial filter of ONE frame: albedo
- * demodulation is fjgpu_denoise_albedo below (without it textured surfaces lean on the colour term), no variance guidance, no temporal reuse.
+ * demodulation is fjgpu_denoise_albedo below (without it textured surfaces lean on the colour term), variance guidance is fjgpu_denoise_variance further below, no temporal reuse.
  *
  * All arithmetic is f32 without fused multiply-adds, sums left to right (csrc/device/fjgpu_denoise_math.h is the one source of the
  * kernel, of the host twin the CPU tests run and of the constants).  h = (1/16, 1/4, 3/8, 1/4, 1/16).  For iteration i = 0 ..
@@ -269,6 +269,44 @@ int fjgpu_denoise(int device, const fjgpu_denoise_desc *desc,
 int fjgpu_denoise_albedo(int device, const fjgpu_denoise_desc *desc, const float *color_in, const float *normal, const float *position,
     const int32_t *ids, const float *albedo /* DEVICE [yres][xres][3] or NULL */, float albedo_floor, float *color_out,
     void *hip_stream, fjgpu_stats *stats);
+
+/* Variance-guided denoising: the filter above with the edge-stopping function of SVGF (Schied et al., HPG 2017, 4.2 and 4.4) in place of
+ * the colour term.  The luminance distance of a tap is measured in units of the local standard deviation, and the variance is filtered
+ * along with the colour, so one sigma_luminance serves noisy and clean pixels alike.  The variance is the caller's (variance_in) or a
+ * spatial estimate from the frame itself under the guides -- what SVGF falls back to for pixels without temporal history.
+ * csrc/device/fjgpu_denoise_var_math.h is the one source of the arithmetic: f32 without fused multiply-adds, sums left to right, one expf
+ * per tap, taps dy outer and dx inner; a tap outside the region is skipped, and so is (stop_at_ids) a tap with ids[q][0] != ids[p][0].
+ * k_n and k_x are those of fjgpu_denoise.  l(C) = 0.2126f C.r + 0.7152f C.g + 0.0722f C.b.
+ *
+ * Estimate (fjgpu_denoise_estimate_variance; fjgpu_denoise_variance with variance_in NULL): for every region pixel p over the taps
+ * q = p + (dx, dy), dx, dy = -3..3, with w = expf(-(d2n k_n + d2x k_x)) (the guides only; the centre weighs 1):
+ *   pass 1: s0 += w, s1 += w l_q, m = s1 / s0;    pass 2, same taps and weights: d = l_q - m, s2 += w (d d);    V = s2 / s0, V = V > 0 ? V : 0.
+ * Iteration i = 0 .. iterations-1, spacing 2^i, colour C and variance V (the estimate or variance_in at i = 0, then the previous outputs):
+ *   g = the 3 x 3 average of V around p at spacing 1, weights k3[dy+1] k3[dx+1], k3 = (1/4, 1/2, 1/4), taps outside the region skipped,
+ *       divided by the sum of the weights used (no id stop);
+ *   k_l = 1.f / (sigma_luminance sqrtf(g) + 1e-6f), or 0.f (term off) for sigma_luminance <= 0 or +inf; it does not halve per iteration --
+ *       the variance shrinks by itself;
+ *   e = fabsf(l_q - l_p) k_l + d2n k_n + d2x k_x,  w = (h[dy+2] h[dx+2]) expf(-e) over the 5 x 5 taps,
+ *   sum += w C_q (four channels), wsum += w, vsum += (w w) V_q;   C' = sum / wsum,  V' = vsum / (wsum wsum).
+ * With sigma_luminance = 0 the colours are fjgpu_denoise's with sigma_color = 0, bit for bit.
+ *
+ * desc->sigma_color is ignored by both entries (a NaN is still refused), desc->iterations by the estimate.  Only region pixels of any buffer
+ * are read or written.  The variance buffers are DEVICE [yres][xres] f32; variance_in must be finite and >= 0.  color_out may equal
+ * color_in; variance_out must not overlap variance_in or a colour buffer (equal pointers are refused).  With albedo (fjgpu_denoise_albedo's
+ * demodulation, same kernels) the order is demodulate, estimate on the demodulated frame, iterate, remodulate, and the variances are
+ * those of the demodulated luminance.  Scratch per call: fjgpu_denoise's plus two f32 planes of the region.  stats: gen_ms covers the guide
+ * pack, the demodulation and the estimate, resolve_ms the iterations and the remodulation, batches = iterations (0 for the estimate alone).
+ * Errors: those of fjgpu_denoise_albedo and a NaN sigma_luminance, each message naming the function called; FJGPU_ENODEV when no device
+ * is visible. */
+int fjgpu_denoise_estimate_variance(int device, const fjgpu_denoise_desc *desc,
+    const float *color, const float *normal, const float *position, const int32_t *ids,
+    float *variance_out /* DEVICE [yres][xres] f32 */, void *hip_stream, fjgpu_stats *stats);
+
+int fjgpu_denoise_variance(int device, const fjgpu_denoise_desc *desc, float sigma_luminance,
+    const float *color_in, const float *normal, const float *position, const int32_t *ids,
+    const float *albedo /* or NULL */, float albedo_floor,
+    const float *variance_in  /* DEVICE [yres][xres] f32, or NULL: estimated as above */,
+    float *color_out, float *variance_out /* or NULL */, void *hip_stream, fjgpu_stats *stats);
 
 /* Tunables (all have defaults): "batch_tiles" tiles per wavefront batch, "batch_samples" samples per batch where batch_tiles is 0
  * (0, the default: as many as the memory budget holds -- fastest where frames repeat; a caller that renders one frame per scene
