@@ -23,6 +23,7 @@
 #include "fjgpu_build.h"
 #include "fjgpu_denoise.h"
 #include "fjgpu_denoise_variance.h"
+#include "fjgpu_temporal.h"
 #include "fjgpu_kernels.h"
 #include "fjgpu_lbvh.h"
 #include "fjgpu_light_cone.h"
@@ -152,6 +153,7 @@ struct fjgpu_scene {
   DScene S;                        // device pointers inside
   DeviceBuffers mem;               // scene-lifetime allocations
   double cam_fov;
+  fj_camera_desc camera;           // the desc the scene was created with or last set to (fjgpu_scene_get_camera / fjgpu_scene_set_camera)
   int n_light_samples;
   // options
   long batch_tiles;
@@ -896,6 +898,7 @@ static int upload_scene(const fj_scene_desc *desc, fjgpu::HostScene &hs, int dev
   S.cam_znear = hs.cam_znear;
   S.cam_zfar = hs.cam_zfar;
   sc->cam_fov = hs.cam_fov;
+  sc->camera = desc->camera;
   sc->n_light_samples = S.n_light_samples;
   sc->max_children = 0;
   sc->uses_sample_uid = S.has_motion || S.cam_xform != nullptr || S.has_area;
@@ -2553,6 +2556,204 @@ int fjgpu_camera_samples(fjgpu_scene *sc, const fj_render_desc *r, int tile_id, 
     rays8[8 * i + 6] = S.cam_znear; rays8[8 * i + 7] = S.cam_zfar;      // the range of a camera ray (Camera::GetRay, src/fj_camera.cc:105-106)
   }
   return (int) n;
+}
+
+// fjgpu_denoise_estimate_variance of the frame divided by its albedo: the first stage of fjgpu_denoise_variance with an albedo (the same
+// launches in the same order) with the estimate as the result -- the spatial fallback of fjgpu_denoise_temporal, whose moments are those of
+// the demodulated luminance.
+int fjgpu_denoise_estimate_variance_albedo(int device, const fjgpu_denoise_desc *d, const float *color, const float *normal, const float *position,
+    const int32_t *ids, const float *albedo, float albedo_floor, float *variance_out, void *hip_stream, fjgpu_stats *stats)
+{
+  if (!albedo) return fjgpu_denoise_estimate_variance(device, d, color, normal, position, ids, variance_out, hip_stream, stats);
+  const char *fn = "fjgpu_denoise_estimate_variance_albedo";
+  if (!(std::isfinite(albedo_floor) && albedo_floor > 0)) return fail(FJGPU_EINVAL, std::string(fn) + ": albedo_floor must be finite and > 0");
+  if (!d || !color || !variance_out)
+    return fail(FJGPU_EINVAL, std::string(fn) + ": null argument (desc, color and variance_out are required)");
+  if (const int e = dnv_check(fn, d, color, false)) return e;
+  if ((const void *) variance_out == (const void *) color || (const void *) variance_out == (const void *) albedo)
+    return fail(FJGPU_EINVAL, std::string(fn) + ": variance_out must not be the colour or the albedo buffer");
+  if (fjgpu_device_count() < 1) return fail(FJGPU_ENODEV, std::string(fn) + ": no HIP device is visible");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const int w = d->region[2] - d->region[0], h = d->region[3] - d->region[1];
+  const size_t npx = (size_t) w * (size_t) h;
+  const int stop = (d->stop_at_ids && ids) ? 1 : 0;
+  DeviceBuffers W;
+  float *d_guide, *d_dem;
+  if (W.alloc(npx * 8, &d_guide) || W.alloc(npx * 4, &d_dem)) return fail(FJGPU_ENOMEM, std::string(fn) + ": device allocation failed");
+  fjgpu_stats acc;
+  std::memset(&acc, 0, sizeof(acc));
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int rc = 0;
+  for (int k = 0; k < 2 && !rc; k++) if (hipEventCreate(&ev[k]) != hipSuccess) rc = -1;
+  const size_t origin = (size_t) d->region[1] * (size_t) d->xres + (size_t) d->region[0];
+  if (!rc) {
+    (void) hipEventRecord(ev[0], st);
+    rc = launch_dn_demodulate(st, color + origin * 4, d->xres, albedo, d->xres, d->region[0], d->region[1], albedo_floor, d_dem, w, w, h);
+    if (!rc) rc = launch_dn_pack_var(st, d_dem, w, normal, position, ids, d->xres, d->region[0], d->region[1], w, h, d_guide);
+    if (!rc) rc = launch_dn_variance(st, d_guide, variance_out + origin, d->xres, w, h, stop,
+                                     fj_dn_constants(0.f, normal ? d->sigma_normal : 0.f, position ? d->sigma_position : 0.f, 0));
+    (void) hipEventRecord(ev[1], st);
+  }
+  const hipError_t se = hipStreamSynchronize(st);      // (also before the transient buffers go away)
+  if (rc == 0 && se == hipSuccess) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) acc.gen_ms = acc.total_ms = ms;
+  }
+  for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
+  if (rc) return fail(FJGPU_ENODEV, std::string(fn) + ": HIP failure: " + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
+  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string(fn) + ": stream synchronize: " + hipGetErrorString(se));
+  if (stats) *stats = acc;
+  return 0;
+}
+
+// ---- camera of a resident scene.  Host state only: the four fields every render call copies into its launch parameters.
+int fjgpu_scene_get_camera(const fjgpu_scene *sc, fj_camera_desc *out)
+{
+  if (!sc || !out) return fail(FJGPU_EINVAL, "fjgpu_scene_get_camera: null argument");
+  *out = sc->camera;
+  return 0;
+}
+
+int fjgpu_scene_set_camera(fjgpu_scene *sc, const fj_camera_desc *camera)
+{
+  if (!sc || !camera) return fail(FJGPU_EINVAL, "fjgpu_scene_set_camera: null argument");
+  const fj_xform_desc &cx = camera->xform;
+  for (const int cnt : {cx.n_translate, cx.n_rotate, cx.n_scale})
+    if (cnt < 1 || cnt > FJ_MAX_XFORM_SAMPLES) return fail(FJGPU_EINVAL, "fjgpu_scene_set_camera: camera transform sample count out of range");
+  if (cx.n_translate != 1 || cx.n_rotate != 1 || cx.n_scale != 1)
+    return fail(FJGPU_EUNSUPPORTED, "fjgpu_scene_set_camera: a time-sampled camera is not supported (static cameras only)");
+  if (sc->S.cam_xform)
+    return fail(FJGPU_EUNSUPPORTED, "fjgpu_scene_set_camera: the scene was created with a time-sampled camera (its buffers and random streams were sized for that)");
+  // what BuildHostScene derives from desc->camera and upload_scene copies, with the same statements
+  double M[16], Minv[16];
+  fjgpu::MakeTransform(cx, 0, M, Minv);
+  std::memcpy(sc->S.cam_M, M, sizeof(sc->S.cam_M));
+  sc->S.cam_znear = camera->znear;
+  sc->S.cam_zfar = camera->zfar;
+  sc->cam_fov = camera->fov;
+  sc->camera = *camera;
+  return 0;
+}
+
+int fjgpu_scene_view(const fjgpu_scene *sc, const fj_render_desc *r, fjgpu_view *out)
+{
+  if (!sc || !r || !out) return fail(FJGPU_EINVAL, "fjgpu_scene_view: null argument");
+  if (r->sampler_type == 1) return fail(FJGPU_EUNSUPPORTED, "fjgpu_scene_view: the adaptive sampler is not supported (fixed-grid sampler only)");
+  if (r->sampler_type != 0) return fail(FJGPU_EINVAL, "unknown sampler_type");
+  if (const char *why = bad_render(r)) return fail(FJGPU_EINVAL, why);
+  if (sc->S.cam_xform) return fail(FJGPU_EUNSUPPORTED, "fjgpu_scene_view: a time-sampled camera is not supported (static cameras only)");
+  if (sc->S.has_motion) return fail(FJGPU_EUNSUPPORTED, "fjgpu_scene_view: a scene with motion (time-sampled transforms or vertex velocities) is not supported (static scenes only)");
+  double M[16], Minv[16];
+  fjgpu::MakeTransform(sc->camera.xform, 0, M, Minv);
+  std::memcpy(out->world_to_camera, Minv, sizeof(out->world_to_camera));
+  // (Renderer::preprocess_camera + Camera::compute_uv_size), as render_tiles_once sets it
+  const double aspect = r->xres / (double) r->yres;
+  out->uv_size[1] = fjgpu::CameraUvSizeY(sc->cam_fov);
+  out->uv_size[0] = out->uv_size[1] * aspect;
+  out->xres = r->xres; out->yres = r->yres;
+  return 0;
+}
+
+// ---- temporal accumulation (fjgpu_temporal.hip, fjgpu_temporal_math.h).  One launch, no scratch: every refusal is decided before a device call.
+namespace {
+
+bool tp_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+  if (!a || !b) return false;
+  const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+}  // namespace
+
+int fjgpu_denoise_temporal(int device, const fjgpu_temporal_desc *d, const float *color, const float *position, const float *normal,
+    const int32_t *ids, const float *albedo, const float *variance_spatial, const fjgpu_view *prev_view, const float *prev_position,
+    const float *prev_normal, const int32_t *prev_ids, const fjgpu_temporal_history *prev, const fjgpu_temporal_history *next,
+    float *variance_out, void *hip_stream, fjgpu_stats *stats)
+{
+  const std::string f("fjgpu_denoise_temporal");
+  if (!d || !color) return fail(FJGPU_EINVAL, f + ": null argument (desc and color are required)");
+  if (!position || !normal || !ids) return fail(FJGPU_EINVAL, f + ": null guide (position, normal and ids are required: without them there is nothing to reproject)");
+  if (!next || !next->color || !next->moments || !next->length) return fail(FJGPU_EINVAL, f + ": null history (next and its three buffers are required)");
+  if (prev && (!prev->color || !prev->moments || !prev->length)) return fail(FJGPU_EINVAL, f + ": null history (prev is set, so are its three buffers)");
+  if (prev && (!prev_view || !prev_position || !prev_normal || !prev_ids))
+    return fail(FJGPU_EINVAL, f + ": null previous frame (prev is set: prev_view, prev_position, prev_normal and prev_ids are required)");
+  if (d->xres <= 0 || d->yres <= 0) return fail(FJGPU_EINVAL, f + ": resolution must be positive");
+  if (d->region[0] < 0 || d->region[1] < 0 || d->region[2] > d->xres || d->region[3] > d->yres ||
+      d->region[0] >= d->region[2] || d->region[1] >= d->region[3])
+    return fail(FJGPU_EINVAL, f + ": region must be a non-empty rectangle inside the frame");
+  if (std::isnan(d->alpha_min) || std::isnan(d->max_history) || std::isnan(d->tol_position) || std::isnan(d->cos_normal) ||
+      std::isnan(d->min_history_variance) || std::isnan(d->albedo_floor))
+    return fail(FJGPU_EINVAL, f + ": a parameter is NaN");
+  if (!(d->alpha_min > 0.f && d->alpha_min <= 1.f)) return fail(FJGPU_EINVAL, f + ": alpha_min must be in (0, 1]");
+  if (!(d->max_history >= 1.f)) return fail(FJGPU_EINVAL, f + ": max_history must be >= 1");
+  if (albedo && !(std::isfinite(d->albedo_floor) && d->albedo_floor > 0)) return fail(FJGPU_EINVAL, f + ": albedo_floor must be finite and > 0");
+  if (prev && (prev_view->xres <= 0 || prev_view->yres <= 0)) return fail(FJGPU_EINVAL, f + ": prev_view's resolution must be positive");
+  if (((uintptr_t) color | (uintptr_t) next->color | (uintptr_t) (prev ? prev->color : nullptr)) & 15u)
+    return fail(FJGPU_EINVAL, f + ": colour buffers must be 16-byte aligned");
+  if (d->region[3] - d->region[1] > 65535 * 16) return fail(FJGPU_EINVAL, f + ": a region of more than 1048560 rows");
+  {
+    const size_t px = (size_t) d->xres * (size_t) d->yres * sizeof(float);
+    const struct { const void *p; size_t n; } outs[4] = {{next->color, 4 * px}, {next->moments, 2 * px}, {next->length, px}, {variance_out, px}};
+    const struct { const void *p; size_t n; } ins[12] = {{color, 4 * px}, {position, 3 * px}, {normal, 3 * px}, {ids, 4 * px}, {albedo, 3 * px},
+        {variance_spatial, px}, {prev ? prev_position : nullptr, 3 * px}, {prev ? prev_normal : nullptr, 3 * px}, {prev ? prev_ids : nullptr, 4 * px},
+        {prev ? prev->color : nullptr, 4 * px}, {prev ? prev->moments : nullptr, 2 * px}, {prev ? prev->length : nullptr, px}};
+    for (int a = 0; a < 4; a++) {
+      for (int b = 0; b < 12; b++)
+        if (tp_overlap(outs[a].p, outs[a].n, ins[b].p, ins[b].n))
+          return fail(FJGPU_EINVAL, f + ": an output buffer (next, variance_out) overlaps prev or an input");
+      for (int b = a + 1; b < 4; b++)
+        if (tp_overlap(outs[a].p, outs[a].n, outs[b].p, outs[b].n)) return fail(FJGPU_EINVAL, f + ": output buffers (next, variance_out) overlap each other");
+    }
+  }
+  if (fjgpu_device_count() < 1) return fail(FJGPU_ENODEV, f + ": no HIP device is visible");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+
+  TpParams k;
+  std::memset(&k, 0, sizeof(k));
+  if (prev) {
+    std::memcpy(k.w2c, prev_view->world_to_camera, sizeof(k.w2c));
+    k.uv_size[0] = prev_view->uv_size[0]; k.uv_size[1] = prev_view->uv_size[1];
+    k.view_xres = prev_view->xres; k.view_yres = prev_view->yres;
+  }
+  k.xres = d->xres; k.yres = d->yres;
+  k.x0 = d->region[0]; k.y0 = d->region[1]; k.x1 = d->region[2]; k.y1 = d->region[3];
+  k.alpha_min = d->alpha_min; k.max_history = d->max_history;
+  k.min_history_variance = d->min_history_variance; k.albedo_floor = d->albedo_floor;
+  fj_tp_terms(d->tol_position, d->cos_normal, &k);
+  TpBuffers B;
+  std::memset(&B, 0, sizeof(B));
+  B.color = color; B.position = position; B.normal = normal; B.ids = ids; B.albedo = albedo; B.variance_spatial = variance_spatial;
+  if (prev) {
+    B.prev_position = prev_position; B.prev_normal = prev_normal; B.prev_ids = prev_ids;
+    B.prev_color = prev->color; B.prev_moments = prev->moments; B.prev_length = prev->length;
+  }
+  B.next_color = next->color; B.next_moments = next->moments; B.next_length = next->length;
+  B.variance_out = variance_out;
+
+  fjgpu_stats acc;
+  std::memset(&acc, 0, sizeof(acc));
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int rc = 0;
+  for (int e = 0; e < 2 && !rc; e++) if (hipEventCreate(&ev[e]) != hipSuccess) rc = -1;
+  if (!rc) {
+    (void) hipEventRecord(ev[0], st);
+    rc = launch_tp_accumulate(st, k, B);
+    (void) hipEventRecord(ev[1], st);
+  }
+  const hipError_t se = hipStreamSynchronize(st);
+  if (rc == 0 && se == hipSuccess) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) acc.resolve_ms = acc.total_ms = ms;
+    acc.batches = 1;
+  }
+  for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
+  if (rc) return fail(FJGPU_ENODEV, f + ": HIP failure: " + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
+  if (se != hipSuccess) return fail(FJGPU_ENODEV, f + ": stream synchronize: " + hipGetErrorString(se));
+  if (stats) *stats = acc;
+  return 0;
 }
 
 }  // extern "C"

@@ -1,0 +1,15 @@
+// fjgpu_temporal.h -- launcher of the temporal accumulation's kernel (fjgpu_temporal.hip); the C entry point fjgpu_denoise_temporal is in
+// fjgpu_api.hip
+#ifndef FJGPU_TEMPORAL_H
+#define FJGPU_TEMPORAL_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "fjgpu_temporal_math.h"
+
+// one launch over the region of `k`: every buffer of `B` is DEVICE memory, pixel (0, 0) of the frame; no output may overlap an input.
+// Returns 0 or the hipError_t of the launch.
+int launch_tp_accumulate(hipStream_t st, const TpParams &k, const TpBuffers &B);
+
+#endif

@@ -68,6 +68,48 @@ class DenoiseDesc(C.Structure):       # fjgpu_denoise_desc
     ]
 
 
+MAX_XFORM_SAMPLES = 8                  # FJ_MAX_XFORM_SAMPLES
+
+
+class XformSample(C.Structure):        # fj_xform_sample
+    _fields_ = [("v", C.c_double * 3), ("time", C.c_double)]
+
+
+class XformDesc(C.Structure):          # fj_xform_desc
+    _fields_ = [
+        ("transform_order", C.c_int32), ("rotate_order", C.c_int32),
+        ("n_translate", C.c_int32), ("n_rotate", C.c_int32), ("n_scale", C.c_int32), ("_pad", C.c_int32),
+        ("translate", XformSample * MAX_XFORM_SAMPLES), ("rotate", XformSample * MAX_XFORM_SAMPLES),
+        ("scale", XformSample * MAX_XFORM_SAMPLES),
+    ]
+
+
+class CameraDesc(C.Structure):         # fj_camera_desc
+    _fields_ = [("xform", XformDesc), ("fov", C.c_double), ("znear", C.c_double), ("zfar", C.c_double)]
+
+    def copy(self):
+        out = CameraDesc()
+        C.memmove(C.byref(out), C.byref(self), C.sizeof(CameraDesc))
+        return out
+
+
+class View(C.Structure):               # fjgpu_view
+    _fields_ = [("world_to_camera", C.c_double * 12), ("uv_size", C.c_double * 2), ("xres", C.c_int32), ("yres", C.c_int32)]
+
+
+class TemporalHistory(C.Structure):    # fjgpu_temporal_history: DEVICE pointers
+    _fields_ = [(n, C.c_void_p) for n in ("color", "moments", "length")]
+
+
+class TemporalDesc(C.Structure):       # fjgpu_temporal_desc
+    _fields_ = [
+        ("xres", C.c_int32), ("yres", C.c_int32),
+        ("region", C.c_int32 * 4),
+        ("alpha_min", C.c_float), ("max_history", C.c_float), ("tol_position", C.c_float), ("cos_normal", C.c_float),
+        ("min_history_variance", C.c_float), ("albedo_floor", C.c_float),
+    ]
+
+
 class RenderStats(C.Structure):        # fj_render_stats
     _fields_ = [("render_seconds", C.c_double), ("prepare_seconds", C.c_double), ("rays", RayCounts)]
 

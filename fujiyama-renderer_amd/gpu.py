@@ -45,6 +45,15 @@ def lib():
                                                       C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
         L.fjgpu_denoise_variance.argtypes = [C.c_int, C.POINTER(ffi.DenoiseDesc), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
+        L.fjgpu_denoise_estimate_variance_albedo.argtypes = [C.c_int, C.POINTER(ffi.DenoiseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
+        L.fjgpu_scene_get_camera.argtypes = [C.c_void_p, C.POINTER(ffi.CameraDesc)]
+        L.fjgpu_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(ffi.CameraDesc)]
+        L.fjgpu_scene_view.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.POINTER(ffi.View)]
+        L.fjgpu_denoise_temporal.argtypes = [C.c_int, C.POINTER(ffi.TemporalDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(ffi.View), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(ffi.TemporalHistory), C.POINTER(ffi.TemporalHistory), C.c_void_p, C.c_void_p,
+                                             C.POINTER(ffi.GpuStats)]
         L.fjgpu_camera_samples.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_int, C.c_void_p, C.c_int]
         L.fjgpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.fjgpu_global_option.argtypes = [C.c_char_p, C.c_long]
@@ -233,6 +242,34 @@ class Scene(object):
         out, info["denoise_stats"] = denoise(fb, aov["normal"], aov["position"], aov["ids"], region=region, device=self._device,
                                              stream=stream, out=fb, **kw)
         return out, info
+
+    def get_camera(self):
+        """the camera the scene renders with (include/fjgpu.h: fjgpu_scene_get_camera) -> ffi.CameraDesc, a copy"""
+        cam = ffi.CameraDesc()
+        _check(lib().fjgpu_scene_get_camera(self._h, C.byref(cam)))
+        return cam
+
+    def set_camera(self, camera=None, translate=None, rotate=None, fov=None):
+        """Move the camera of the resident scene (include/fjgpu.h: fjgpu_scene_set_camera): host state only, no device work, no BLAS
+        build; every later render, trace and AOV call gives what a scene created with that camera gives.  camera: an ffi.CameraDesc
+        (None: the current one); translate / rotate (three numbers each) and fov then override its first sample.  Static cameras
+        only.  -> the ffi.CameraDesc that was set."""
+        cam = self.get_camera() if camera is None else camera.copy()
+        if translate is not None:
+            cam.xform.translate[0].v[:] = tuple(float(v) for v in translate)
+        if rotate is not None:
+            cam.xform.rotate[0].v[:] = tuple(float(v) for v in rotate)
+        if fov is not None:
+            cam.fov = float(fov)
+        _check(lib().fjgpu_scene_set_camera(self._h, C.byref(cam)))
+        return cam
+
+    def view(self, render):
+        """what it takes to find a world point in the frame the current camera renders with `render` (include/fjgpu.h: fjgpu_scene_view;
+        the projection is written out there) -> ffi.View"""
+        v = ffi.View()
+        _check(lib().fjgpu_scene_view(self._h, C.byref(render), C.byref(v)))
+        return v
 
     def camera_samples(self, render, tile_id):
         """the camera rays of one tile as the AOV and beauty passes trace them (include/fjgpu.h: fjgpu_camera_samples) ->
@@ -454,6 +491,222 @@ def denoise_variance(color, normal=None, position=None, ids=None, albedo=None, v
     if return_variance:
         return out.cpu().numpy(), variance_out.cpu().numpy(), st
     return out.cpu().numpy(), st
+
+
+def _estimate_variance_device(color, normal, position, ids, albedo, albedo_floor, region, sigma_normal, sigma_position, stop_at_ids, device,
+                              stream):
+    """estimate_variance() of device tensors with the result left on the device, of colour / albedo where there is an albedo
+    (include/fjgpu.h: fjgpu_denoise_estimate_variance_albedo) -> (float32 tensor [H, W], GpuStats)"""
+    import torch
+    dev = torch.device("cuda", device)
+    hw = tuple(color.shape[:2])
+    var = torch.zeros(hw, dtype=torch.float32, device=dev)
+    d = _denoise_desc(hw, region, 1, sigma_normal, sigma_position, stop_at_ids)
+    torch.cuda.synchronize(dev)          # the fill ran on torch's stream
+    st = ffi.GpuStats()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _check(lib().fjgpu_denoise_estimate_variance_albedo(device, C.byref(d), ptr(color), ptr(normal), ptr(position), ptr(ids), ptr(albedo),
+                                                        C.c_float(float(albedo_floor)), ptr(var), C.c_void_p(stream or 0), C.byref(st)))
+    return var, st
+
+
+def estimate_variance_albedo(color, albedo, normal=None, position=None, ids=None, albedo_floor=ALBEDO_FLOOR, region=None,
+                             sigma_normal=SIGMA_NORMAL, sigma_position=None, stop_at_ids=True, device=0, stream=None):
+    """estimate_variance() of colour / max(albedo, albedo_floor) (include/fjgpu.h: fjgpu_denoise_estimate_variance_albedo): the variance
+    of the demodulated luminance, what temporal_accumulate() takes as variance_spatial next to an albedo -> (numpy [H, W] float32, GpuStats)"""
+    import torch
+    dev = torch.device("cuda", device)
+    c = _device_tensor(color, "color", torch.float32, 4, dev)
+    hw = tuple(c.shape[:2])
+    var, st = _estimate_variance_device(c, _device_tensor(normal, "normal", torch.float32, 3, dev, hw),
+                                        _device_tensor(position, "position", torch.float32, 3, dev, hw),
+                                        _device_tensor(ids, "ids", torch.int32, 4, dev, hw), _device_tensor(albedo, "albedo", torch.float32, 3, dev, hw),
+                                        albedo_floor, region, sigma_normal, sigma_position, stop_at_ids, device, stream)
+    return var.cpu().numpy(), st
+
+
+# the defaults of temporal_accumulate() and TemporalDenoiser: of the grid in profiles/temporal_pass.txt (a six-frame sub-pixel pan of the
+# 64 x 48 Cornell box at 2 x 2 spp against a 12 x 12 spp frame of the last camera, CPU oracle and numpy model, scripts/temporal_grid.py)
+# the setting with the smallest mean squared error of the last frame (demodulated chain) among those that keep a history on at least 90 %
+# of the foreground: the position tolerance has to span a pixel of a surface seen at a grazing angle (0.02 of the diagonal keeps 84 %, 0.05
+# keeps 99 %).  Six frames reach neither 1 / ALPHA_MIN nor MAX_HISTORY.  MIN_HISTORY_VARIANCE is SVGF's: shorter histories take the spatial
+# estimate.  What accumulation does NOT buy on that frame without a colour clamp and a sampler seed is written out in the same file.
+ALPHA_MIN = 0.1
+MAX_HISTORY = 32.0
+MIN_HISTORY_VARIANCE = 4.0
+COS_NORMAL = 0.97
+TOL_POSITION_FRACTION = 0.05        # of the diagonal of the foreground's bounding box (TemporalDenoiser)
+
+HISTORY_NAMES = ("color", "moments", "length")
+HISTORY_CHANNELS = {"color": 4, "moments": 2, "length": 1}
+
+
+def _history_tensors(h, name, dev, hw, fresh):
+    """{name: device tensor} of a history given as a dict of numpy arrays or tensors (length as [H, W] or [H, W, 1]); fresh: new zeroed ones"""
+    import torch
+    if fresh:
+        return {n: torch.zeros(hw + ((HISTORY_CHANNELS[n],) if n != "length" else ()), dtype=torch.float32, device=dev) for n in HISTORY_NAMES}
+    out = {}
+    for n in HISTORY_NAMES:
+        if n == "length":
+            out[n] = _variance_tensor(h[n], "%s['length']" % name, dev, hw)
+        else:
+            out[n] = _device_tensor(h[n], "%s[%r]" % (name, n), torch.float32, HISTORY_CHANNELS[n], dev, hw)
+    return out
+
+
+def _history_struct(t):
+    h = ffi.TemporalHistory()
+    for n in HISTORY_NAMES:
+        setattr(h, n, t[n].data_ptr())
+    return h
+
+
+def temporal_accumulate(color, position, normal, ids, albedo=None, variance_spatial=None, prev_view=None, prev_position=None,
+                        prev_normal=None, prev_ids=None, prev=None, next=None, region=None, alpha_min=ALPHA_MIN, max_history=MAX_HISTORY,
+                        tol_position=None, cos_normal=COS_NORMAL, min_history_variance=MIN_HISTORY_VARIANCE, albedo_floor=ALBEDO_FLOOR,
+                        device=0, stream=None, variance_out=None, to_host=True):
+    """Temporal accumulation of a beauty frame (include/fjgpu.h: fjgpu_denoise_temporal) -> (history, variance, GpuStats): history =
+    {"color": [H, W, 4], "moments": [H, W, 2], "length": [H, W]}, variance [H, W], as numpy arrays -- or, with to_host=False, as the
+    float32 tensors on the device the call wrote.  color [H, W, 4], position / normal [H, W, 3], ids [H, W, 4] int32 (Scene.render_aov's)
+    and the optional albedo [H, W, 3] and variance_spatial [H, W] describe the current frame; prev_view (Scene.view of the previous
+    camera), prev_position, prev_normal, prev_ids and prev (a history as returned) the previous one -- prev None: the first frame of a
+    sequence.  numpy arrays are uploaded, device tensors used where they are.  next / variance_out: a history of contiguous float32
+    device tensors / a tensor [H, W] to write instead of new ones (pixels outside the region are left as they are; new ones are 0
+    there); they must not be prev's or an input's.  tol_position is in world units (None, <= 0 or +inf: off), cos_normal <= -1: off."""
+    import torch
+    dev = torch.device("cuda", device)
+    c = _device_tensor(color, "color", torch.float32, 4, dev)
+    hw = tuple(c.shape[:2])
+    p = _device_tensor(position, "position", torch.float32, 3, dev, hw)
+    n = _device_tensor(normal, "normal", torch.float32, 3, dev, hw)
+    i = _device_tensor(ids, "ids", torch.int32, 4, dev, hw)
+    a = _device_tensor(albedo, "albedo", torch.float32, 3, dev, hw)
+    vs = _variance_tensor(variance_spatial, "variance_spatial", dev, hw)
+    pp = _device_tensor(prev_position, "prev_position", torch.float32, 3, dev, hw)
+    pn = _device_tensor(prev_normal, "prev_normal", torch.float32, 3, dev, hw)
+    pi = _device_tensor(prev_ids, "prev_ids", torch.int32, 4, dev, hw)
+    hp = None if prev is None else _history_tensors(prev, "prev", dev, hw, False)
+    if next is None:
+        hn = _history_tensors(None, "next", dev, hw, True)
+    else:
+        hn = {k: next[k] for k in HISTORY_NAMES}
+        for k, t in hn.items():
+            want = hw + ((HISTORY_CHANNELS[k],) if k != "length" else ())
+            if not (torch.is_tensor(t) and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == want):
+                raise ValueError("next[%r] must be a contiguous float32 tensor %s on the device" % (k, want))
+    if variance_out is None:
+        variance_out = torch.zeros(hw, dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(variance_out) and variance_out.device == dev and variance_out.dtype == torch.float32 and
+              variance_out.is_contiguous() and tuple(variance_out.shape) == hw):
+        raise ValueError("variance_out must be a contiguous float32 tensor [H, W] on the device")
+    d = ffi.TemporalDesc()
+    d.yres, d.xres = hw
+    d.region[:] = (0, 0, d.xres, d.yres) if region is None else tuple(int(v) for v in region)
+    d.alpha_min, d.max_history = float(alpha_min), float(max_history)
+    d.tol_position = 0.0 if tol_position is None else float(tol_position)
+    d.cos_normal, d.min_history_variance, d.albedo_floor = float(cos_normal), float(min_history_variance), float(albedo_floor)
+    torch.cuda.synchronize(dev)          # uploads and fills ran on torch's stream
+    st = ffi.GpuStats()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    h_prev = None if hp is None else C.byref(_history_struct(hp))
+    h_next = _history_struct(hn)
+    _check(lib().fjgpu_denoise_temporal(device, C.byref(d), ptr(c), ptr(p), ptr(n), ptr(i), ptr(a), ptr(vs),
+                                        None if prev_view is None else C.byref(prev_view), ptr(pp), ptr(pn), ptr(pi), h_prev,
+                                        C.byref(h_next), ptr(variance_out), C.c_void_p(stream or 0), C.byref(st)))
+    if to_host:
+        return {k: t.cpu().numpy() for k, t in hn.items()}, variance_out.cpu().numpy(), st
+    return hn, variance_out, st
+
+
+class TemporalDenoiser(object):
+    """A sequence of frames of one resident scene -- a turntable, a fly-through of a static set -- denoised with the history of the frames
+    before (include/fjgpu.h: fjgpu_denoise_temporal in front of fjgpu_denoise_variance).  render(camera) runs, with every buffer on the
+    device: Scene.set_camera; the beauty pass into a device framebuffer; one AOV call (position, normal, ids and, with demodulate, albedo);
+    the spatial variance estimate of the current frame; temporal_accumulate against the previous frame's guides, view and history (the
+    histories ping-pong between two sets of buffers); denoise_variance(variance=the temporal variance) on the accumulated colour.  The
+    only copy to the host is the result's.  `params` are temporal_accumulate's alpha_min, max_history, tol_position, cos_normal,
+    min_history_variance and denoise_variance's sigma_luminance, iterations, sigma_normal, sigma_position, stop_at_ids, albedo_floor.
+    tol_position / sigma_position not given: TOL_POSITION_FRACTION / SIGMA_POSITION_FRACTION_VARIANCE of the diagonal of the bounding
+    box of the first frame's foreground (a frame without foreground switches the terms off).  The limits are the entry's: static scene,
+    static camera per frame, fixed-grid sampler; frames from one and the same camera are identical and gain nothing."""
+
+    _TEMPORAL = ("alpha_min", "max_history", "tol_position", "cos_normal", "min_history_variance")
+    _FILTER = ("sigma_luminance", "iterations", "sigma_normal", "sigma_position", "stop_at_ids")
+
+    def __init__(self, scene, render, demodulate=True, stream=None, **params):
+        for k in params:
+            if k not in self._TEMPORAL + self._FILTER + ("albedo_floor",):
+                raise ValueError("unknown parameter %r" % k)
+        self.scene, self.render_desc, self.demodulate, self.stream = scene, render.copy(), bool(demodulate), stream
+        self.params = dict(params)
+        self.albedo_floor = float(self.params.pop("albedo_floor", ALBEDO_FLOOR))
+        self.frames = 0
+        self._prev = None            # (view, aov tensors, history tensors) of the frame before
+        self._spare = None           # the history buffers the next frame writes
+
+    def reset(self):
+        """drop the history: the next frame is the first of a sequence"""
+        self._prev = None
+        self.frames = 0
+
+    def render(self, camera=None, keep_inputs=False):
+        """one frame -> (numpy [H, W, 4] float32, info).  camera: an ffi.CameraDesc, or a dict of Scene.set_camera's overrides, or None
+        (the scene's current camera).  info: "beauty_stats", "aov_stats", "estimate_stats", "temporal_stats", "denoise_stats" (GpuStats),
+        "tol_position", "sigma_position" (the values used), "frame" (0 for the first of a sequence) and, with keep_inputs, "beauty",
+        "aov", "accumulated", "history_length" [H, W] and "variance" [H, W] (the temporal pass's) as numpy copies."""
+        import torch
+        sc, r = self.scene, self.render_desc
+        dev = torch.device("cuda", sc._device)
+        region = tuple(int(v) for v in r.region)
+        if camera is not None:
+            sc.set_camera(**camera) if isinstance(camera, dict) else sc.set_camera(camera)
+        view = sc.view(r)            # (the refusals of the AOV pass, before anything is rendered)
+        fb = torch.zeros((r.yres, r.xres, 4), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)          # the fill ran on torch's stream
+        st_beauty = sc.render_tiles(r, None, fb.data_ptr(), stream=self.stream)
+        want = ("position", "normal", "ids") + (("albedo",) if self.demodulate else ())
+        aov, st_aov = sc._render_aov_device(r, want=want, stream=self.stream, names=AOV_ALL if self.demodulate else AOV_NAMES)
+        p = self.params
+        if "tol_position" not in p or p.get("sigma_position") is None:
+            x0, y0, x1, y1 = region
+            pos = aov["position"][y0:y1, x0:x1].reshape(-1, 3)
+            keep = (aov["ids"][y0:y1, x0:x1, 0].reshape(-1) >= 0) & torch.isfinite(pos).all(dim=1)
+            diag = 0.0
+            if bool(keep.any()):
+                q = pos[keep].double()
+                diag = float(torch.linalg.norm(q.max(dim=0).values - q.min(dim=0).values))
+            p.setdefault("tol_position", TOL_POSITION_FRACTION * diag)
+            if p.get("sigma_position") is None:
+                p["sigma_position"] = SIGMA_POSITION_FRACTION_VARIANCE * diag
+        tkw = {k: p[k] for k in self._TEMPORAL if k in p}
+        fkw = {k: p[k] for k in self._FILTER if k in p}
+        albedo = aov.get("albedo")
+        var_s, st_est = _estimate_variance_device(fb, aov["normal"], aov["position"], aov["ids"], albedo, self.albedo_floor, region,
+                                                  fkw.get("sigma_normal", SIGMA_NORMAL), fkw["sigma_position"], fkw.get("stop_at_ids", True),
+                                                  sc._device, self.stream)
+        prev = self._prev
+        hist, var_t, st_tmp = temporal_accumulate(
+            fb, aov["position"], aov["normal"], aov["ids"], albedo=albedo, variance_spatial=var_s,
+            prev_view=prev[0] if prev else None, prev_position=prev[1]["position"] if prev else None,
+            prev_normal=prev[1]["normal"] if prev else None, prev_ids=prev[1]["ids"] if prev else None, prev=prev[2] if prev else None,
+            next=self._spare, region=region, albedo_floor=self.albedo_floor, device=sc._device, stream=self.stream, to_host=False, **tkw)
+        out = torch.zeros_like(fb)
+        res, st_dn = denoise_variance(hist["color"], aov["normal"], aov["position"], aov["ids"], albedo=albedo, variance=var_t, region=region,
+                                      device=sc._device, stream=self.stream, out=out, albedo_floor=self.albedo_floor, **fkw)
+        info = dict(beauty_stats=st_beauty, aov_stats=st_aov, estimate_stats=st_est, temporal_stats=st_tmp, denoise_stats=st_dn,
+                    tol_position=p["tol_position"], sigma_position=p["sigma_position"], frame=self.frames)
+        if keep_inputs:
+            info["beauty"] = fb.cpu().numpy()
+            info["aov"] = {name: t.cpu().numpy() for name, t in aov.items()}
+            info["accumulated"] = hist["color"].cpu().numpy()
+            info["history_length"] = hist["length"].cpu().numpy()
+            info["variance"] = var_t.cpu().numpy()
+        # ping-pong: what this frame read is what the next one writes
+        self._spare = prev[2] if prev else None
+        self._prev = (view, aov, hist)
+        self.frames += 1
+        return res, info
 
 
 def global_option(name, value):

@@ -218,7 +218,7 @@ int fjgpu_camera_samples(fjgpu_scene *scene, const fj_render_desc *render, int t
 
 /* Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010) over a beauty frame, guided by the
  * feature buffers of fjgpu_render_aov.  Device buffers in, device buffers out; no scene handle.  A spatial filter of ONE frame: albedo
- * demodulation is fjgpu_denoise_albedo below (without it textured surfaces lean on the colour term), variance guidance is fjgpu_denoise_variance further below, no temporal reuse.
+ * demodulation is fjgpu_denoise_albedo below (without it textured surfaces lean on the colour term), variance guidance is fjgpu_denoise_variance further below, reuse of earlier frames is fjgpu_denoise_temporal below that.
  *
  * All arithmetic is f32 without fused multiply-adds, sums left to right (csrc/device/fjgpu_denoise_math.h is the one source of the
  * kernel, of the host twin the CPU tests run and of the constants).  h = (1/16, 1/4, 3/8, 1/4, 1/16).  For iteration i = 0 ..
@@ -307,6 +307,105 @@ int fjgpu_denoise_variance(int device, const fjgpu_denoise_desc *desc, float sig
     const float *albedo /* or NULL */, float albedo_floor,
     const float *variance_in  /* DEVICE [yres][xres] f32, or NULL: estimated as above */,
     float *color_out, float *variance_out /* or NULL */, void *hip_stream, fjgpu_stats *stats);
+
+/* The estimate of the frame divided by its albedo: the first stage of fjgpu_denoise_variance with an albedo -- demodulate (fjgpu_denoise_albedo's
+ * statements), then the estimate above -- with the estimate as the result.  It is the variance of the demodulated luminance, the quantity the
+ * moments of fjgpu_denoise_temporal describe, and so that call's variance_spatial where an albedo is in use.  albedo NULL:
+ * fjgpu_denoise_estimate_variance, bit for bit.  Scratch: the guide records and one RGBA frame of the region.  Errors: those of
+ * fjgpu_denoise_estimate_variance, the messages naming this function; FJGPU_EINVAL for an albedo_floor that is not finite and > 0 and for a
+ * variance_out that is the albedo buffer. */
+int fjgpu_denoise_estimate_variance_albedo(int device, const fjgpu_denoise_desc *desc,
+    const float *color, const float *normal, const float *position, const int32_t *ids,
+    const float *albedo /* DEVICE [yres][xres][3] or NULL */, float albedo_floor,
+    float *variance_out /* DEVICE [yres][xres] f32 */, void *hip_stream, fjgpu_stats *stats);
+
+/* Camera of a resident scene.  A sequence over a static set -- a turntable, a fly-through -- moves nothing but the camera, and the camera is
+ * host-side state of the scene that every render call copies into its launch parameters: setting it costs no device work and no BLAS build.
+ * get: the camera the scene renders with -- the desc it was created with, or last set to.
+ * set: recomputes what fjgpu_scene_create derives from desc->camera for a static camera, with the same statements (the transform's matrix
+ * at time 0, fov, znear, zfar) and touches nothing else: not the work arena, the options, the counters, the light cones or the sort grid.
+ * After set(c) every render, trace, AOV and camera-sample call gives the bits and the ray counts of a scene freshly created with camera c.
+ * Errors: FJGPU_EINVAL for a NULL argument and for a sample count outside 1..FJ_MAX_XFORM_SAMPLES ("camera transform sample count out of
+ * range", as at creation); FJGPU_EUNSUPPORTED, the reason in the message, for a camera with more than one sample in any channel and for a
+ * scene that was created with a time-sampled camera (its buffers and random streams were sized for that). */
+int fjgpu_scene_get_camera(const fjgpu_scene *scene, fj_camera_desc *out);
+int fjgpu_scene_set_camera(fjgpu_scene *scene, const fj_camera_desc *camera);
+
+/* The view of a frame: what it takes to find a world point in the frame the scene's current camera renders with `render`.  No device work.
+ * With the conventions of Camera::GetRay and FixedGridSampler::generate_samples -- u = (x + .5) / xres, v = 1 - (y + .5) / yres, the ray's
+ * target ((u - .5) uv_size_x, (v - .5) uv_size_y, -1) in camera space -- the projection of the world point P is, in f64,
+ *   c  = world_to_camera * (P, 1);   visible only if c.z < 0
+ *   fx = (c.x / -c.z / uv_size[0] + .5) * xres - .5
+ *   fy = (.5 - c.y / -c.z / uv_size[1]) * yres - .5
+ * so a point seen through the centre of pixel (x, y) projects to (fx, fy) = (x, y).
+ * Errors: the static-camera refusals of fjgpu_render_aov (adaptive sampler, time-sampled camera, scene with motion), FJGPU_EINVAL for NULL. */
+typedef struct fjgpu_view {
+  double world_to_camera[12];   /* rows of the 3 x 4 inverse of the camera's transform (the Minv of MakeTransform) */
+  double uv_size[2];            /* Camera::compute_uv_size with aspect = xres / yres, as the render calls set it    */
+  int32_t xres, yres;
+} fjgpu_view;
+int fjgpu_scene_view(const fjgpu_scene *scene, const fj_render_desc *render, fjgpu_view *out);
+
+/* Temporal accumulation (SVGF, Schied et al., HPG 2017, 4.1): the frame in front of fjgpu_denoise_variance for a SEQUENCE of a static scene.
+ * The world position of every pixel is projected into the previous frame; the history found there -- accumulated colour, the first and
+ * second moment of luminance, the history length -- is fetched bilinearly from the taps that still show the same surface and the new
+ * frame is blended in.  The running mean over N frames is worth about N times the samples, and its moments are a per-pixel variance of the
+ * pixel's own values over time: what variance_in of fjgpu_denoise_variance is for.  Device buffers in and out; no scene handle.
+ * csrc/device/fjgpu_temporal_math.h is the one source of the arithmetic (kernel, host twin of the CPU tests; tests/temporal_model.py
+ * restates it): f32 without fused multiply-adds, sums left to right, the projection alone in f64.
+ *
+ * For every region pixel p with colour C, guides P, N and I = ids[p][0]:
+ *   luminance   L = l(D), l of fjgpu_denoise_variance; D = C.rgb / max(albedo, albedo_floor) per channel where there is an albedo, else C.rgb.
+ *               The accumulated colour itself stays modulated: it is a beauty frame.
+ *   no history  C' = C, m1 = L, m2 = L L, len = 1: where prev is NULL, I < 0 (background), P is not finite, the projection is not visible or
+ *               not finite, or the valid weight below is <= 1e-4f.
+ *   fetch       (fx, fy) = P through prev_view as above; x0 = floor(fx), y0 = floor(fy), a = (float) (fx - x0), b = (float) (fy - y0); the taps
+ *               q = (x0 + i, y0 + j), j outer, i inner, weigh (i ? a : 1 - a) * (j ? b : 1 - b).  A tap is valid if it lies in the region,
+ *               prev_ids[q][0] == I, |prev_position[q] - P|^2 <= tol_position^2, dot(prev_normal[q], N) >= cos_normal and prev->length[q] >= 1
+ *               (a comparison with a NaN fails; a term that is off compares nothing).  H_colour (4), H_moments (2), H_len: the weighted
+ *               sums over the valid taps, each divided by the valid weight.
+ *   blend       n = min(H_len + 1, max_history), alpha = max(1 / n, alpha_min), X' = H + alpha (X - H) for X in {C, (L, L L)}; len' = n.
+ *   variance    v = max(0, m2' - m1' m1'); where n < min_history_variance and variance_spatial is given, v = variance_spatial[p] (SVGF's
+ *               fallback: fjgpu_denoise_estimate_variance of the current frame).
+ * Only region pixels of any buffer are read or written.  `next` and variance_out must not overlap `prev`, each other or any input -- the
+ * fetch reads arbitrary previous pixels -- : equal or overlapping buffers are refused.  color, prev->color and next->color are 16-byte
+ * aligned.  One kernel launch, no scratch, about 170 bytes of compulsory traffic per pixel with an albedo.  Work is enqueued on `hip_stream`
+ * and the call returns after the stream has been synchronised.  stats (may be NULL): resolve_ms = total_ms, batches = 1.
+ * Errors: FJGPU_EINVAL, every message starting "fjgpu_denoise_temporal:", for a NULL desc, colour, guide (position, normal, ids and the
+ * previous frame's three where prev is set), prev_view (where prev is set), next or member of a history; an invalid region; alpha_min
+ * outside (0, 1]; max_history < 1; a NaN parameter; an albedo_floor that is not finite and > 0 where there is an albedo; overlapping
+ * buffers; a misaligned colour pointer; a prev_view whose resolution is not positive.  All of them are decided before any device call.
+ * FJGPU_ENODEV when no device is visible.
+ *
+ * Limits.  Static scenes, a static camera per frame and the fixed-grid sampler: those of the AOV pass, whose buffers this reads.  Nothing
+ * that moves with the camera on a surface is reprojected -- reflections, refractions, highlights, shadows of moving lights: the colour history
+ * of a glass pixel follows the glass surface, not what is seen through it.  The sampler has no seed: two frames from the same camera are
+ * identical and accumulating them gains nothing; the gain comes from the sub-pixel motion of a moving camera (a seed for the sampler and
+ * the shaders' draws would be a change to the production path).  There is no Si* entry: the reference's interface has no such call. */
+typedef struct fjgpu_temporal_history {   /* DEVICE pointers, row-major xres*yres */
+  float *color;        /* [4]  accumulated RGBA                                  */
+  float *moments;      /* [2]  first and second moment of (demodulated) luminance */
+  float *length;       /* [1]  history length, >= 1 on every pixel written        */
+} fjgpu_temporal_history;
+
+typedef struct fjgpu_temporal_desc {
+  int32_t xres, yres;            /* row-major frame the buffers describe                                          */
+  int32_t region[4];             /* xmin ymin xmax ymax: the convention (and validation) of fjgpu_denoise_desc    */
+  float   alpha_min;             /* in (0, 1]: the least weight of the new frame (1: no accumulation)             */
+  float   max_history;           /* >= 1: the history length saturates here                                       */
+  float   tol_position;          /* world units; <= 0 or +inf: term off                                           */
+  float   cos_normal;            /* <= -1: term off                                                               */
+  float   min_history_variance;  /* shorter histories take variance_spatial (where given)                         */
+  float   albedo_floor;          /* fjgpu_denoise_albedo's; ignored where `albedo` is NULL                        */
+} fjgpu_temporal_desc;
+
+int fjgpu_denoise_temporal(int device, const fjgpu_temporal_desc *desc,
+    /* current frame  */ const float *color, const float *position, const float *normal, const int32_t *ids,
+                         const float *albedo /* [3] or NULL */, const float *variance_spatial /* [yres][xres] or NULL */,
+    /* previous frame */ const fjgpu_view *prev_view, const float *prev_position, const float *prev_normal, const int32_t *prev_ids,
+                         const fjgpu_temporal_history *prev /* NULL: first frame */,
+    /* out            */ const fjgpu_temporal_history *next, float *variance_out /* [yres][xres] or NULL */,
+    void *hip_stream, fjgpu_stats *stats);
 
 /* Tunables (all have defaults): "batch_tiles" tiles per wavefront batch, "batch_samples" samples per batch where batch_tiles is 0
  * (0, the default: as many as the memory budget holds -- fastest where frames repeat; a caller that renders one frame per scene
