@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -27,6 +28,7 @@
 #include "fjgpu_kernels.h"
 #include "fjgpu_lbvh.h"
 #include "fjgpu_light_cone.h"
+#include "fjgpu_light_hull.h"
 #include "fjgpu_raysort.h"
 #include "fjgpu_tlas.h"
 
@@ -164,6 +166,10 @@ struct fjgpu_scene {
   long light_cones = 1;            // option "light_cones" (default 1): the light loop of whole-ray launches settles box misses with the per-light shadow cones built at
                                    // scene creation (fjgpu_light_cone.h); 0: the instantiation without them, the same pairs through the box test
   int cone_rows = 0, cone_records = 0;   // queries "light_cone_rows" / "light_cone_records": groups with a row in the table, records of them with a plane
+  long light_hulls = 1;            // option "light_hulls" (default 1): the cone instantiation of the light loop settles the pairs outside the light's hull cone (fjgpu_light_hull.h)
+                                   // before the box is consulted: unoccluded, neither box-tested nor queued; 0: the box cones alone
+  int hull_rows = 0, hull_records = 0;   // queries "light_hull_rows" / "light_hull_records"
+  unsigned long long hull_verdicts = 0;  // query "light_hull_verdicts": pairs the hull cones settled in the last render call (counting frames, option count_nodes; else 0)
   long count_all_shadow;           // option "count_all_shadow" (default 1): light records of weight zero reach the light loop, which counts their shadow rays as the
                                    // reference does; it never queues them (their colour is exactly zero), so nothing walks them.  0: k_shade drops such records (other counts)
   // queries "stack_peak" / "stack_peak_closest" / "stack_peak_shadow": the most entries any lane's traversal stack held in the launches of the
@@ -493,6 +499,112 @@ int fjgpu_tile_rect(const fj_render_desc *render, int tile_id, int32_t rect[4])
 
 }  // extern "C"
 
+// per-light hull cones (fjgpu_light_hull.h): one record per (single-instance group whose instance is a static mesh, point light sample), from
+// the world images of ALL vertices of the mesh -- two passes over them per light, on worker threads.  Time-sampled transforms, vertex
+// velocities, curve sets, groups of several instances, area lights and dome samples get none (the box cones exclude the same cases).
+// hulls: rows of one record per light sample; rows[g]: the row of group g or -1.  cone_reach[g]: the reach of the group's box cones or -1.
+static void build_light_hull_rows(const fjgpu::HostScene &hs, const std::vector<double> &cone_reach, std::vector<DLightCone> &hulls,
+    std::vector<int32_t> &rows, int *n_rows, int *n_records)
+{
+  const size_t nl = hs.light_samples.size();
+  rows.assign(hs.groups.size(), -1);
+  hulls.clear();
+  if (!hs.area_lights.empty()) return;      // (a scene with a rectangle or sphere light runs the light loop's general instantiation: nothing would read the table)
+  for (size_t g = 0; g < hs.groups.size() && nl; g++) {
+    if (hs.groups[g].n_instances != 1) continue;
+    const DInstance &I = hs.instances[hs.group_members[hs.group_member_first[g]]];
+    const fjgpu::HostPrimSet &ps = hs.primsets[I.primset];
+    if (I.xform >= 0 || ps.type != FJ_PRIMSET_MESH || !ps.mesh || ps.mesh->velocity || ps.mesh->n_points <= 0) continue;
+    std::vector<size_t> lights;                 // the samples with a fixed position near enough to have a cone at all
+    for (size_t l = 0; l < nl; l++) if (hs.light_samples[l].type == FJ_POINT_LIGHT) lights.push_back(l);
+    if (lights.empty()) continue;
+    const size_t nv = (size_t) ps.mesh->n_points, nk = lights.size();
+    // vertex ranges of a fixed size (the sums and maxima do not depend on the number of threads), claimed by the workers
+    const size_t chunk = 16384, nchunks = (nv + chunk - 1) / chunk;
+    // (at most 16 workers, fewer where OMP_NUM_THREADS says so: a process is often given a part of the machine hardware_concurrency() reports)
+    size_t workers = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    if (const char *omp = getenv("OMP_NUM_THREADS")) { const long v = atol(omp); if (v >= 1) workers = std::min<size_t>(workers, (size_t) v); }
+    const unsigned hc = (unsigned) std::max<size_t>(1, std::min(workers, nchunks));
+    auto over_chunks = [&](const std::function<void(size_t)> &fn) {
+      std::atomic<size_t> next(0);
+      std::vector<std::thread> th;
+      for (unsigned t = 0; t < hc; t++) th.emplace_back([&]() { for (size_t c; (c = next.fetch_add(1)) < nchunks;) fn(c); });
+      for (auto &t : th) t.join();
+    };
+    std::vector<double> W(3 * nv), csum(3 * nchunks, 0.);
+    over_chunks([&](size_t c) {
+      double s[3] = {0., 0., 0.};
+      for (size_t i = c * chunk; i < std::min(nv, (c + 1) * chunk); i++) {
+        light_hull_world(I.M, ps.mesh->P + 3 * i, &W[3 * i]);
+        for (int k = 0; k < 3; k++) s[k] += W[3 * i + k];
+      }
+      for (int k = 0; k < 3; k++) csum[3 * c + k] = s[k];
+    });
+    double ctr[3] = {0., 0., 0.};
+    for (size_t c = 0; c < nchunks; c++) for (int k = 0; k < 3; k++) ctr[k] += csum[3 * c + k];
+    for (int k = 0; k < 3; k++) ctr[k] /= (double) nv;
+    std::vector<LightHullAcc> acc(nk), part(nk * nchunks);
+    for (size_t k = 0; k < nk; k++) light_hull_frame(hs.light_samples[lights[k]].P, ctr, &acc[k]);
+    over_chunks([&](size_t c) {
+      for (size_t k = 0; k < nk; k++) {
+        LightHullAcc A = acc[k];
+        for (size_t i = c * chunk; i < std::min(nv, (c + 1) * chunk) && A.ok; i++) light_hull_add(&A, &W[3 * i]);
+        part[k * nchunks + c] = A;
+      }
+    });
+    for (size_t k = 0; k < nk; k++) for (size_t c = 0; c < nchunks; c++) light_hull_merge(&acc[k], &part[k * nchunks + c]);
+    const size_t at = hulls.size();
+    hulls.resize(at + nl);
+    std::memset(&hulls[at], 0, nl * sizeof(DLightCone));
+    std::vector<char> open(nk, 1);
+    std::vector<uint32_t> bad(nk * nchunks);
+    for (int round = 0; round <= FJ_LH_WIDENINGS; round++) {
+      bool any = false;
+      for (size_t k = 0; k < nk; k++) if (open[k]) { if (light_hull_finish(&acc[k], hs.groups[g].sbounds, &hulls[at + lights[k]])) any = true; else open[k] = 0; }
+      if (!any) break;
+      // the verify pass: the finished normals against every vertex
+      over_chunks([&](size_t c) {
+        for (size_t k = 0; k < nk; k++) {
+          uint32_t b = 0;
+          if (open[k]) for (size_t i = c * chunk; i < std::min(nv, (c + 1) * chunk); i++) b |= light_hull_verify(&hulls[at + lights[k]], acc[k].Pl, &W[3 * i]);
+          bad[k * nchunks + c] = b;
+        }
+      });
+      for (size_t k = 0; k < nk; k++) {
+        if (!open[k]) continue;
+        uint32_t b = 0;
+        for (size_t c = 0; c < nchunks; c++) b |= bad[k * nchunks + c];
+        if (!b) open[k] = 0;                                 // verified: the record stands
+        else light_hull_widen(&acc[k], b);
+      }
+    }
+    for (size_t k = 0; k < nk; k++) if (open[k]) std::memset(&hulls[at + lights[k]], 0, sizeof(DLightCone));      // still failing after the last widening
+    int built = 0;
+    double reach = 1e300;
+    for (size_t l = 0; l < nl; l++) if (hulls[at + l].count > 0) { built++; reach = std::min(reach, hulls[at + l].reach); }
+    if (!built) { hulls.resize(at); continue; }
+    // (read once per wave iteration: the row's smallest -- and no larger than the reach of the group's box cones: the light loop keeps one
+    // set of lanes within reach for both tables)
+    if (g < cone_reach.size() && cone_reach[g] >= 0) reach = std::min(reach, cone_reach[g]);
+    for (size_t l = 0; l < nl; l++) hulls[at + l].reach = reach;
+    rows[g] = (int32_t) (at / nl);
+    (*n_rows)++; *n_records += built;
+  }
+}
+
+// the reach of group g's row of box cones as upload_scene builds it (the smallest of its records' reaches), or -1: no row
+static double box_cone_row_reach(const fjgpu::HostScene &hs, size_t g)
+{
+  if (hs.groups[g].n_instances != 1) return -1.;
+  double reach = 1e300;
+  int built = 0;
+  for (const DLightSample &LS : hs.light_samples) {
+    DLightCone C;
+    if ((LS.type == FJ_POINT_LIGHT || LS.type == FJ_DOME_LIGHT) && light_cone_build(LS.P, hs.groups[g].sbounds, &C) > 0) { built++; reach = std::min(reach, C.reach); }
+  }
+  return built ? reach : -1.;
+}
+
 // Upload a built host scene to one device (fjgpu_scene_create = build + upload; the multi-device
 // entry builds once and uploads to every device).
 static int upload_scene(const fj_scene_desc *desc, fjgpu::HostScene &hs, int device, fjgpu_scene **out)
@@ -784,10 +896,12 @@ static int upload_scene(const fj_scene_desc *desc, fjgpu::HostScene &hs, int dev
   // per-light shadow cones (fjgpu_light_cone.h): one record per (single-instance group, light sample) whose position the light loop uses as it
   // stands -- point and dome samples; grid and sphere lights draw theirs per shading event.  Lights and instance boxes are fixed for the scene's life.
   S.light_cones = nullptr; S.cone_rows = nullptr;
+  std::vector<double> cone_reach;        // per group: the reach of its row of box cones, -1: no row
   {
     const size_t nl = hs.light_samples.size();
     std::vector<int32_t> rows(hs.groups.size(), -1);
     std::vector<DLightCone> cones;
+    cone_reach.assign(hs.groups.size(), -1.);
     for (size_t g = 0; g < hs.groups.size() && nl; g++) {
       if (hs.groups[g].n_instances != 1) continue;
       const size_t at = cones.size();
@@ -804,11 +918,23 @@ static int upload_scene(const fj_scene_desc *desc, fjgpu::HostScene &hs, int dev
       if (!built) { cones.resize(at); continue; }
       for (size_t l = 0; l < nl; l++) cones[at + l].reach = reach;       // (read once per wave iteration: the row's smallest)
       rows[g] = (int32_t) (at / nl);
+      cone_reach[g] = reach;
       sc->cone_rows++; sc->cone_records += built;
     }
     if (!cones.empty()) {
       e |= M.upload(cones.data(), cones.size(), &S.light_cones);
       e |= M.upload(rows.data(), rows.size(), &S.cone_rows);
+    }
+  }
+  // per-light hull cones: the second table (build_light_hull_rows above)
+  S.light_hulls = nullptr; S.hull_rows = nullptr;
+  {
+    std::vector<int32_t> rows;
+    std::vector<DLightCone> hulls;
+    build_light_hull_rows(hs, cone_reach, hulls, rows, &sc->hull_rows, &sc->hull_records);
+    if (!hulls.empty()) {
+      e |= M.upload(hulls.data(), hulls.size(), &S.light_hulls);
+      e |= M.upload(rows.data(), rows.size(), &S.hull_rows);
     }
   }
   S.has_area = hs.area_lights.empty() ? 0 : 1;
@@ -1030,6 +1156,34 @@ int fjgpu_host_instance_level(const fj_scene_desc *desc, int group, int32_t *out
   return G.count;
 }
 
+int fjgpu_host_light_hulls(const fj_scene_desc *desc, int group, void *out_records, double *out_Pl, int cap, double *out_M)
+{
+  if (!desc || group < 0 || group >= desc->n_groups) return fail(FJGPU_EINVAL, "bad light-hull query");
+  fjgpu::HostScene hs;
+  std::string err;
+  const int e = fjgpu::BuildHostScene(desc, &hs, &err, true);
+  if (e) return fail(e, err);
+  std::vector<int32_t> rows;
+  std::vector<DLightCone> hulls;
+  int n_rows = 0, n_records = 0;
+  std::vector<double> cone_reach(hs.groups.size(), -1.);       // (the uploaded records carry the smaller of the two rows' reaches: the same here)
+  for (size_t g = 0; g < hs.groups.size(); g++) cone_reach[g] = box_cone_row_reach(hs, g);
+  build_light_hull_rows(hs, cone_reach, hulls, rows, &n_rows, &n_records);
+  if (out_M) {
+    if (hs.groups[group].n_instances != 1) return fail(FJGPU_EINVAL, "light-hull query: the group has several instances");
+    std::memcpy(out_M, hs.instances[hs.group_members[hs.group_member_first[group]]].M, 12 * sizeof(double));
+  }
+  const size_t nl = hs.light_samples.size();
+  for (size_t l = 0; l < nl && (int) l < cap; l++) {
+    if (out_records) {
+      if (rows[group] >= 0) std::memcpy((char *) out_records + l * sizeof(DLightCone), &hulls[(size_t) rows[group] * nl + l], sizeof(DLightCone));
+      else std::memset((char *) out_records + l * sizeof(DLightCone), 0, sizeof(DLightCone));
+    }
+    if (out_Pl) for (int k = 0; k < 3; k++) out_Pl[3 * l + k] = hs.light_samples[l].P[k];
+  }
+  return (int) nl;
+}
+
 int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value)
 {
   if (!scene || !name || !value) return fail(FJGPU_EINVAL, "bad query call");
@@ -1083,6 +1237,18 @@ int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value)
     if (hipSetDevice(scene->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(FJGPU_ENODEV, "hipSetDevice / hipDeviceSynchronize");
     light_cone_validate_counts(&v, &c);
     *value = n == "light_cone_verdicts" ? v : c;
+    return 0;
+  }
+  // per-light hull cones: groups with a row, records with planes, the pairs they settled in the last counting frame; and, in a
+  // -DFJ_LIGHT_HULL_VALIDATE build, the settled pairs walked since the library was loaded and how many of those walks found a hit
+  if (n == "light_hull_rows") { *value = scene->hull_rows; return 0; }
+  if (n == "light_hull_records") { *value = scene->hull_records; return 0; }
+  if (n == "light_hull_verdicts" || n == "light_hull_contradictions") {
+    double v = -1, c = -1;
+    if (hipSetDevice(scene->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(FJGPU_ENODEV, "hipSetDevice / hipDeviceSynchronize");
+    light_hull_validate_counts(&v, &c);
+    if (n == "light_hull_verdicts") *value = v >= 0 ? v : (double) scene->hull_verdicts;
+    else *value = c;
     return 0;
   }
   if (n == "has_curves") { *value = scene->S.has_curves; return 0; }
@@ -1171,6 +1337,7 @@ int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value)
   if (n == "count_nodes") { scene->count_events = value != 0; return 0; }
   if (n == "count_all_shadow") { scene->count_all_shadow = value != 0; return 0; }
   if (n == "light_cones") { scene->light_cones = value != 0; return 0; }
+  if (n == "light_hulls") { scene->light_hulls = value != 0; return 0; }
   if (n == "overlap_shadow") {
     if (value < 0 || value > 2) return fail(FJGPU_EINVAL, "overlap_shadow: 0 off, 1 on, 2 by the batch size");
     scene->overlap = value;
@@ -1357,6 +1524,7 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
   HIP_TRY(hipSetDevice(sc->device));
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   sc->stack_peak_closest = sc->stack_peak_shadow = 0;
+  sc->hull_verdicts = 0;
 
   std::vector<fjgpu::TileRect> all;
   fjgpu::GenerateTiles(*r, &all);
@@ -1514,6 +1682,8 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
   S.pad_cs_ = 0;
   swp.compact = S.compact_squeue;
   swp.light_cones = (sc->light_cones && S.light_cones && S.cone_rows) ? 1 : 0;
+  swp.pad_ = 0;
+  swp.light_hulls = (swp.light_cones && sc->light_hulls && S.light_hulls && S.hull_rows) ? 1 : 0;
   swp.queue_capacity = (uint32_t) sc->squeue_cap;
   swp.join_capacity = (swp.pre_resolve && sc->split_shadow && sc->d_join) ? (uint32_t) sc->join_cap : 0u;
   S.shadow_join = swp.join_capacity ? sc->d_join : nullptr;
@@ -1848,6 +2018,7 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
     acc.shadow_nodes += hc.sh_nodes; acc.shadow_prims += hc.sh_prims; acc.shadow_insts += hc.sh_insts;
     sc->stack_peak_closest = std::max(sc->stack_peak_closest, hc.stack_peak);
     sc->stack_peak_shadow = std::max(sc->stack_peak_shadow, hc.sh_stack_peak);
+    sc->hull_verdicts += hc.hull_settled;
     acc.batches++;
     if (sc->batch_fn) {
       // (the stream was synchronised above: the batch's pixels are final in d_fb)

@@ -221,6 +221,9 @@ __device__ void traverse_anyhit(const DScene &S, const DShadowRay *squeue, float
           load_tri(nullptr, (const float *) (S.blas_base + ((size_t) tri_base << 7)), pex & ~AH_PEX_STALL, &v0, &v1, &v2);
           if (tri_ray_anyhit(v0, v1, v2, oo_, od_, tmin, tmax)) {
             have = false; cur = TRAV_DONE; AH_PLEAF_CLEAR();     // occluded: nothing to add
+#ifdef FJ_LIGHT_HULL_VALIDATE
+            lh_validate_occluded(S, squeue, idx, s_accum);
+#endif
 #ifdef FJ_WAVE_TIMELINE
             FJ_TL_RAY(ray_steps);
 #endif
@@ -475,6 +478,9 @@ __device__ void traverse_anyhit(const DScene &S, const DShadowRay *squeue, float
         if (occluded) {
           have = false; cur = TRAV_DONE;     // occluded: nothing to add
           AH_PLEAF_CLEAR();
+#ifdef FJ_LIGHT_HULL_VALIDATE
+          lh_validate_occluded(S, squeue, idx, s_accum);
+#endif
 #ifdef FJ_WAVE_TIMELINE
           FJ_TL_RAY(ray_steps);
 #endif

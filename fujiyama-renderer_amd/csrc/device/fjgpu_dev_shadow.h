@@ -73,6 +73,22 @@ __device__ __forceinline__ int32_t ld_k_i32(const int32_t *p) { return *(const _
 __device__ unsigned long long g_lightcone[2];      // the light loop's cone verdicts, and how many of them the exact test contradicted
 #endif
 
+#ifdef FJ_LIGHT_HULL_VALIDATE
+// debug build: the pairs the hull cones settle are queued all the same, flagged in the compact record's spare word (lean any-hit walk only); the
+// walk adds their colour whatever it finds and counts the flagged rays that find a hit.  [0] flagged entries queued, [1] those with a hit
+__device__ unsigned long long g_lighthull[2];
+__device__ __forceinline__ void lh_validate_occluded(const DScene &S, const DShadowRay *squeue, uint32_t i, float *s_accum)
+{
+  if (!S.compact_squeue || !sq_c(squeue, i)->pad) return;
+  atomicAdd(&g_lighthull[1], 1ull);
+  const DShadowRayC *q = sq_c(squeue, i);
+  float *acc = s_accum + 4 * (size_t) q->sample;
+  if (q->c[0] != 0.f) atomicAdd(acc + 0, q->c[0]);
+  if (q->c[1] != 0.f) atomicAdd(acc + 1, q->c[1]);
+  if (q->c[2] != 0.f) atomicAdd(acc + 2, q->c[2]);
+}
+#endif
+
 #ifndef FJ_CULL_MINB
 #define FJ_CULL_MINB 1
 #endif
@@ -95,6 +111,11 @@ __device__ unsigned long long g_lightcone[2];      // the light loop's cone verd
 // kCone (whole rays, point / dome lights, no hair; ShadowParams.light_cones): a wave iteration whose records share ONE single-instance group with a
 // row in the cone table settles the box misses of its (point, light) pairs with the light's precomputed shadow cone (fjgpu_light_cone.h) -- a few
 // dot products of Ln with wave-uniform normals -- and runs the reciprocals and the six-plane box test for the undecided lanes only, if any.
+// With a row in the HULL table (fjgpu_light_hull.h; ShadowParams.light_hulls) the pairs are put to the light's hull cone first: a point outside
+// one of its planes cannot be shadowed by the instance's mesh -- the pair is unoccluded, adds its colour like a box miss and is neither box-tested
+// nor queued.  The box cone and the box test are consulted only while some lane of the wave is still open.  Counting launches count a settled
+// pair's candidate instance on the spot: the box test counts it where the ray misses the box and the walk where it passes, so insts_tested
+// does not depend on the option.
 template <bool kHair, bool kArea, bool kSplit, bool kNodesLds = false, bool kCone = false>
 __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSplit ? FJ_CULL_MINB_PLAIN : FJ_CULL_MINB_WHOLE)) k_shadow_cull(DScene S, ShadowParams sp, const DLightRec *lrecs,
     uint32_t rec_begin, uint32_t rec_end, float *s_accum, DShadowRay *squeue, DCounters *cnt, int count_events)
@@ -176,8 +197,9 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
         Ps.x > sb[0] + 2e-4 && Ps.x < sb[3] - 2e-4 && Ps.y > sb[1] + 2e-4 && Ps.y < sb[4] - 2e-4 && Ps.z > sb[2] + 2e-4 && Ps.z < sb[5] - 2e-4;
     // The cone row of the iteration (wave-uniform; null: today's path for every pair) and the lanes whose point lies within the row's reach.
     // Lane 0 is active in every iteration.
-    const DLightCone *cone_row = nullptr;
+    const DLightCone *cone_row = nullptr, *hull_row = nullptr;
     bool cone_lane = false;
+    uint32_t s_hull = 0;                   // counting launches: pairs of this iteration the hull cones settled (wave-uniform)
     if (kCone) {
       static_assert(!kCone || (!kHair && !kArea && !kSplit), "the cones serve whole rays to fixed light positions");
       const int grp = active ? R.group : -1;
@@ -187,6 +209,13 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
         if (row >= 0) {
           cone_row = S.light_cones + (size_t) row * nl;
           const double reach = ld_k_f64(&cone_row->reach);
+          cone_lane = active && !deep_inside && fmax(fmax(fabs(Ps.x), fabs(Ps.y)), fabs(Ps.z)) <= reach;
+        }
+        const int hrow = sp.light_hulls ? ld_k_i32(S.hull_rows + g0) : -1;
+        if (hrow >= 0) {
+          hull_row = S.light_hulls + (size_t) hrow * nl;
+          // (ONE set of lanes within reach for both tables: a hull row carries the smaller of the two rows' reaches, fjgpu_api.hip)
+          const double reach = ld_k_f64(&hull_row->reach);
           cone_lane = active && !deep_inside && fmax(fmax(fabs(Ps.x), fabs(Ps.y)), fabs(Ps.z)) <= reach;
         }
       }
@@ -201,6 +230,9 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
     for (uint32_t l = 0; l < nl; l++) {
       bool emit = false;
       DShadowRay q;
+#ifdef FJ_LIGHT_HULL_VALIDATE
+      bool hull_flag = false;
+#endif
       // split mode (DScene.shadow_join): a ray into a group of several instances is queued once per instance
       // whose box it passes; the lane enumerates them over the rounds below
       bool pending = false;
@@ -214,6 +246,8 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
       // (the plane count of the light's cone comes with the sample; its normals -- 36 SGPRs -- are read where they are used, four planes at a time)
       int lc_count = 0;
       if (kCone && cone_row) lc_count = ld_k_i32(&cone_row[l].count);
+      int lh_count = 0;                    // the light's hull record: six planes or none
+      if (kCone && hull_row) lh_count = ld_k_i32(&hull_row[l].count);
       if (active) {
         // (the table is written once at scene creation: read through the constant address space the wave-uniform record comes through the scalar
         // cache into SGPRs -- as a generic pointer it was three vector loads of 64 identical lanes, waited for at the head of every iteration:
@@ -307,12 +341,30 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
           bool maybe_occluded = false;
           if (sp.cast_shadow) {
             r_shadow++;
-            // the light's shadow cone: a point outside one of its planes surely misses the group's box (one-sided contract of fjgpu_light_cone.h;
+            // the light's hull cone first: a point outside one of its planes is unoccluded (one-sided contract of fjgpu_light_hull.h; the candidates
+            // are the box cones': within reach, a colour to carry, a direction without a zero component)
+            bool settled = false;
+            if (kCone && lh_count > 0) {
+              const bool cand = cone_lane && carries && plain_dir(Ln);
+              if (__ballot(cand)) {
+                const double *pn = &hull_row[l].n[0][0];
+                const double m = light_cone_margin(Ln.x, Ln.y, Ln.z);
+#define FJ_LC_PLANE(j) (cand & light_cone_plane_out(ld_k_f64(pn + 3 * (j)), ld_k_f64(pn + 3 * (j) + 1), ld_k_f64(pn + 3 * (j) + 2), Ln.x, Ln.y, Ln.z, m))
+                settled = FJ_LC_PLANE(0) | FJ_LC_PLANE(1) | FJ_LC_PLANE(2) | FJ_LC_PLANE(3);      // (planes 0, 2, 4 of the hexagon and plane 1: all outside the enclosing triangle)
+                if (__ballot(cand && !settled) != 0ull) settled = settled | FJ_LC_PLANE(4) | FJ_LC_PLANE(5);
+#undef FJ_LC_PLANE
+                // (counting launches: the pair's one candidate instance is counted here -- by the box test where the ray misses the box, by the walk
+                // where it passes; a settled pair meets neither)
+                if (count_events) { s_hull += (uint32_t) __popcll(__ballot(settled)); if (settled) r_insts++; }
+              }
+            }
+            const bool boxed = !(kCone && settled);
+            // then the light's shadow cone, for the lanes the hull left open: a point outside one of its planes surely misses the group's box (one-sided contract of fjgpu_light_cone.h;
             // a direction with a zero component and a point beyond the row's reach are not put to it).  The event counted is the parent's: a
             // candidate instance whose box the ray misses.
             bool sure = false;
             if (kCone && lc_count > 0) {
-              const bool cand = cone_lane && carries && plain_dir(Ln);
+              const bool cand = cone_lane && carries && boxed && plain_dir(Ln);
               if (__ballot(cand)) {
                 // Four planes per trip to the scalar cache: one wait for twelve operands, not one per plane.  The build function put the planes
                 // in an order in which the first four settle nearly every pair (all of them where the cone has four sides); planes not in use are zero.
@@ -334,7 +386,7 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
               if (sure) r_insts++;
             }
             // group bounds test + leaf bounds of the instance BVH, as culling (with cones: for the lanes they left undecided, if the wave has any)
-            const bool need = carries && !(kCone && sure);
+            const bool need = carries && boxed && !(kCone && sure);
             bool test = false;
             if (!kCone || __ballot(need)) test = need && !has_negative_zero(Ln);
             if (deep_inside) maybe_occluded = test;
@@ -360,6 +412,12 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
                 if (box_ray_ref_fast(tn_->box, Ps, Ln, winv, plain, .0001, distance)) { maybe_occluded = true; break; }
                 r_insts++;
               }
+            }
+            if (kCone && settled) {
+              maybe_occluded = false;
+#ifdef FJ_LIGHT_HULL_VALIDATE
+              if (sp.compact && sp.pre_resolve) { maybe_occluded = true; hull_flag = true; }
+#endif
             }
           }
           if (maybe_occluded) {
@@ -454,6 +512,10 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
             qc.o[0] = q.o[0]; qc.o[1] = q.o[1]; qc.o[2] = q.o[2];
             qc.c[0] = q.c[0]; qc.c[1] = q.c[1]; qc.c[2] = q.c[2];
             qc.sample = q.sample; qc.group = q.group; qc.tindex = q.tindex; qc.light = l; qc.pad = 0;
+#ifdef FJ_LIGHT_HULL_VALIDATE
+            qc.pad = hull_flag ? 1u : 0u;
+            if (hull_flag) atomicAdd(&g_lighthull[0], 1ull);
+#endif
             ((DShadowRayC *) squeue)[slot] = qc;
           }
           else squeue[slot] = q;
@@ -466,6 +528,7 @@ __global__ void __launch_bounds__(BLOCK, (kHair || kArea) ? FJ_CULL_MINB : (kSpl
       if (kSplit && ncand >= 2) S.shadow_join[jslot1 - 1u] = ncand << 16;
     }
     c_insts += r_insts; c_shadow += r_shadow;
+    if (kCone && s_hull && lane == 0) atomicAdd(&cnt->hull_settled, (unsigned long long) s_hull);
     if (active) {
       float *acc = s_accum + 4 * (size_t) r_sample;
       const float r0v = W[0] * sum[0], r1v = W[1] * sum[1], r2v = W[2] * sum[2];

@@ -67,6 +67,9 @@ struct ShadowParams {
   int32_t compact;             // 1: the queue holds DShadowRayC records (DScene.compact_squeue)
   int32_t light_cones;         // 1: whole-ray launches of scenes with a cone table (DScene.light_cones) settle box misses with the per-light cones
                                // (scene option "light_cones", default 1); 0: the instantiation without them
+  int32_t light_hulls;         // 1: ... and, before the box is consulted, the pairs outside the light's hull cone (DScene.light_hulls; scene option
+                               // "light_hulls", default 1; only with light_cones: the hulls live in the cone instantiation)
+  int32_t pad_;
 };
 
 struct ResolveParams {
@@ -94,6 +97,8 @@ void set_anyhit_filter_off(long v);     // diagnostics: fjgpu_global_option("any
 // -DFJ_LIGHT_CONE_VALIDATE builds: the cone verdicts of the light loop so far (current device) and how many of them the exact test contradicted;
 // other builds: -1, -1
 void light_cone_validate_counts(double *verdicts, double *contradictions);
+// -DFJ_LIGHT_HULL_VALIDATE builds: the hull-settled pairs the any-hit walks have walked so far and how many of those walks found a hit; other builds: -1, -1
+void light_hull_validate_counts(double *verdicts, double *contradictions);
 void debug_phase_stats();     // FJ_PHASE_STATS builds: print and reset the any-hit walk's phase tallies (stderr)
 // threads of the largest persistent grid (sizes per-thread scratch such as the stack overflow area)
 size_t persistent_threads();

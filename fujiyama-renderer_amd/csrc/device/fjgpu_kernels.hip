@@ -464,6 +464,15 @@ void light_cone_validate_counts(double *verdicts, double *contradictions)
 #endif
 }
 
+void light_hull_validate_counts(double *verdicts, double *contradictions)
+{
+  *verdicts = -1; *contradictions = -1;
+#ifdef FJ_LIGHT_HULL_VALIDATE
+  unsigned long long c[2];
+  if (hipMemcpyFromSymbol(c, HIP_SYMBOL(g_lighthull), sizeof(c)) == hipSuccess) { *verdicts = (double) c[0]; *contradictions = (double) c[1]; }
+#endif
+}
+
 void debug_phase_stats()
 {
 #ifdef FJ_TRI_FILTER_VALIDATE

@@ -271,6 +271,10 @@ struct DScene {
   // (The row index is a table of its own and not a DGroup member: the walks copy DGroups verbatim into a fixed LDS budget of 64 bytes each.)
   const DLightCone *light_cones;
   const int32_t *cone_rows;    // [n_groups]
+  // per-light HULL cones (fjgpu_light_hull.h), a second table of the same records and layout: planes around the instance's MESH as seen from the
+  // light, not around its box.  hull_rows[g] is the row of single-instance static mesh group g or -1.  Both null: no group has a row.
+  const DLightCone *light_hulls;
+  const int32_t *hull_rows;    // [n_groups]
   DLightHair *lrec_hair;       // work buffer (set per render call) or null
   uint32_t shadow_queue_cap;   // entries of the shadow-ray queue (a walk never reads past it, whatever the slot counter says)
   uint32_t cam_slot0;          // implicit camera rays: sample slot of ray 0 of the launch (a level walked in chunks)
@@ -396,7 +400,7 @@ struct DCounters {
   unsigned long long nodes, prims, insts, traced, squeued;
   unsigned long long sh_nodes, sh_prims, sh_insts;   // the shadow walk's share of nodes / prims / insts
   unsigned long long stack_peak, sh_stack_peak;      // counting instantiations: most stack entries a lane held, closest-hit / shadow walks (atomicMax)
-  unsigned long long pad0_[1];
+  unsigned long long hull_settled;                   // counting launches of the light loop: pairs its hull cones settled (fjgpu_light_hull.h)
   uint32_t next_count;         // entries appended to the next ray queue                      (line 1)
   uint32_t light_count;        // entries appended to the light-record queue
   uint32_t overflow;

@@ -337,6 +337,26 @@ def host_instance_level(scene_desc_ptr, group):
     return inst, skip, box
 
 
+LIGHT_HULL = np.dtype([("n", np.float64, (6, 3)), ("reach", np.float64), ("count", np.int32), ("pad", np.int32)])
+
+
+def host_light_hulls(scene_desc_ptr, group):
+    """(records [n_light_samples] of LIGHT_HULL, Pl [n_light_samples, 3], M [3, 4]): the hull cones of the single-instance group as scene
+    creation builds them (count 0: no record), the light samples' positions and the instance's object-to-world matrix; no device needed"""
+    L = lib()
+    L.fjgpu_host_light_hulls.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.fjgpu_host_light_hulls.restype = C.c_int
+    n = L.fjgpu_host_light_hulls(scene_desc_ptr, group, None, None, 0, None)
+    if n < 0:
+        _check(n)
+    rec = np.zeros(n, dtype=LIGHT_HULL)
+    Pl = np.zeros((n, 3), dtype=np.float64)
+    M = np.zeros((3, 4), dtype=np.float64)
+    _check(min(0, L.fjgpu_host_light_hulls(scene_desc_ptr, group, rec.ctypes.data_as(C.c_void_p), Pl.ctypes.data_as(C.c_void_p), n,
+                                           M.ctypes.data_as(C.c_void_p))))
+    return rec, Pl, M
+
+
 # the denoiser's defaults: of the grid in profiles/denoise_pass.txt (the 64 x 48 Cornell box at 2 x 2 spp against a 12 x 12 spp frame, CPU
 # oracle and numpy model) the setting with the smallest mean squared error among those that stop at instance ids
 DENOISE_ITERATIONS = 5

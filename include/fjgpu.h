@@ -414,7 +414,9 @@ int fjgpu_denoise_temporal(int device, const fjgpu_temporal_desc *desc,
  * a recursion level on its own stream, concurrent with the next level; "release_work" 1: hand the work arena back to the driver
  * now (the scene stays resident; the next render call allocates again); "light_cones" 1/0 (default 1): the light loop settles the box misses
  * of single-instance shadow groups with the per-light shadow cones built at scene creation (point lights, whole rays; same results, fewer
- * instructions); 0: every pair takes the box test. Returns 0 or FJGPU_EINVAL. */
+ * instructions); 0: every pair takes the box test; "light_hulls" 1/0 (default 1; only with light_cones on): that loop first settles the pairs
+ * whose surface point lies outside the light's hull cone around the instance's mesh -- unoccluded, neither box-tested nor queued (static
+ * single-instance mesh groups, point lights; same results, fewer shadow rays walked); 0: the box cones alone. Returns 0 or FJGPU_EINVAL. */
 int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value);
 
 /* Process-wide options read by fjgpu_scene_create (which stands for the reference's
@@ -477,6 +479,13 @@ int fjgpu_global_option(const char *name, long value);
  * nodes (any out pointer may be NULL); returns the node count, or a negative error. */
 int fjgpu_host_instance_level(const fj_scene_desc *desc, int group, int32_t *out_inst, int32_t *out_skip, double *out_box, int cap);
 
+/* Inspection, no device needed: the per-light hull cones of single-instance `group` as scene creation builds them (fjgpu_light_hull.h): one
+ * 160-byte record per light sample (six plane normals double[6][3], double reach, int32 plane count, int32 pad; count 0 = no record: the
+ * group has no row, or the light none) and the light samples' positions.  Writes at most `cap` of each (either pointer may be NULL);
+ * out_M (or NULL): rows 0..2 of the object-to-world matrix of the group's one instance, 12 doubles.  Returns the number of light samples, or
+ * a negative error. */
+int fjgpu_host_light_hulls(const fj_scene_desc *desc, int group, void *out_records, double *out_Pl, int cap, double *out_M);
+
 /* Facts about the built device scene (for measurement: record sizes of the actual layout).
  * "node_record_bytes" (128; "anyhit_node_record_bytes" 64: the lean any-hit walk reads the quantised
  * twin of a node), "tri_record_bytes" (36 when every mesh is stored as exact f32
@@ -495,7 +504,10 @@ int fjgpu_host_instance_level(const fj_scene_desc *desc, int group, int32_t *out
  * the walks keep in LDS: a peak above a walk's figure went through the global overflow area), "light_cone_rows" / "light_cone_records" (single-instance
  * groups with a row in the shadow-cone table; records of those rows that hold a cone), "light_cone_verdicts" / "light_cone_contradictions" (a
  * -DFJ_LIGHT_CONE_VALIDATE build: cone verdicts of the light loop since the library was loaded, and how many the exact box test contradicted;
- * -1 in any other build).  Returns 0 or FJGPU_EINVAL. */
+ * -1 in any other build), "light_hull_rows" / "light_hull_records" (the same for the hull-cone table), "light_hull_verdicts" (pairs the hull
+ * cones settled in the last render call with count_nodes on, else 0; a -DFJ_LIGHT_HULL_VALIDATE build: the settled pairs queued and walked
+ * all the same since the library was loaded), "light_hull_contradictions" (that build: how many of those walks found a hit; -1 in any other
+ * build).  Returns 0 or FJGPU_EINVAL. */
 int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value);
 
 /* Diagnostics: the host-side math that feeds geometry to the device (matrices,
