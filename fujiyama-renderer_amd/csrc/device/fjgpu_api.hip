@@ -1184,6 +1184,13 @@ int fjgpu_host_light_hulls(const fj_scene_desc *desc, int group, void *out_recor
   return (int) nl;
 }
 
+int fjgpu_build_config(const char *name, double *value)
+{
+  if (!name || !value) return fail(FJGPU_EINVAL, "bad build_config call");
+  if (!kernels_build_config(name, value)) return fail(FJGPU_EINVAL, std::string("unknown build_config name ") + name);
+  return 0;
+}
+
 int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value)
 {
   if (!scene || !name || !value) return fail(FJGPU_EINVAL, "bad query call");
@@ -1206,6 +1213,7 @@ int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value)
   if (n == "stack_lds") { *value = FJ_STACK_LDS; return 0; }
   if (n == "stack_lds_anyhit") { *value = FJ_STACK_LDS_ANYHIT; return 0; }
   if (n == "stack_lds_curves") { *value = FJ_STACK_LDS_CURVES; return 0; }
+  if (n == "stack_lds_canyhit") { *value = FJ_STACK_LDS_CANYHIT; return 0; }
   if (n == "stack_lds_min") { *value = FJ_STACK_LDS_MIN; return 0; }
   // 1: shadow rays are walked by k_shadow_anyhit (every occluder opaque, no curves, no motion), 0: by k_shadow_trace
   // 1: shadow rays are walked by k_shadow_anyhit_curves (curve scene, every occluder opaque, no motion, instance level within the curve budget)
@@ -1250,6 +1258,19 @@ int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value)
     if (n == "light_hull_verdicts") *value = v >= 0 ? v : (double) scene->hull_verdicts;
     else *value = c;
     return 0;
+  }
+  // -DFJ_TRI_FILTER_VALIDATE build: the verdicts of the lean any-hit walk's f32 triangle filter since the library was loaded (or since the
+  // FJGPU_PHASE_STATS print last reset them), the hits of the exact test behind them and the verdicts it contradicted; other builds: -1.  Read only.
+  {
+    static const char *const tf[5] = {"tri_filter_miss", "tri_filter_hit", "tri_filter_maybe", "tri_filter_exact_hits", "tri_filter_contradictions"};
+    for (int k = 0; k < 5; k++)
+      if (n == tf[k]) {
+        double c[5];
+        if (hipSetDevice(scene->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(FJGPU_ENODEV, "hipSetDevice / hipDeviceSynchronize");
+        tri_filter_validate_counts(c);
+        *value = c[k];
+        return 0;
+      }
   }
   if (n == "has_curves") { *value = scene->S.has_curves; return 0; }
   if (n == "has_motion") { *value = scene->S.has_motion; return 0; }

@@ -526,6 +526,7 @@ __device__ void traverse_anyhit(const DScene &S, const DShadowRay *squeue, float
 #define FJ_ANYHIT_MINB_MULTI 5          // (96 VGPRs, no spill: C2 without the split 134.5 -> 124.1 ms; with the split 117.9)
 #endif
 static_assert((FJ_STACK_LDS_ANYHIT * BLOCK * 4) % 8 == 0, "the object-space rays behind the LDS stack are doubles");
+static_assert(BLOCK * 4 == 1 << 10, "AH_OVF and CA_OVF find the stack row of an LDS address with >> 10");
 template <bool kCount, bool kMulti>
 __global__ void __launch_bounds__(BLOCK, kMulti ? FJ_ANYHIT_MINB_MULTI : FJ_ANYHIT_MINB) k_shadow_anyhit(DScene S, const DShadowRay *squeue, float *s_accum,
     DCounters *cnt, TravTune tune)

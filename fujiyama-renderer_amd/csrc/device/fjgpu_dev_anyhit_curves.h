@@ -23,9 +23,7 @@
 //             of the instance) than any other phase could serve
 // State per lane: 9 slab constants, the node array, five words of cursors -- the object-space ray sits in LDS behind the stack (only
 // the leaf and ribbon phases read it), so the ribbon phase has the register file to itself: no spill at 4 waves per SIMD.
-#ifndef FJ_STACK_LDS_CANYHIT
-#define FJ_STACK_LDS_CANYHIT 16           // stack entries per lane in LDS (deeper ones: the global overflow area); >= FJ_STACK_LDS_MIN
-#endif
+// (FJ_STACK_LDS_CANYHIT, fjgpu_types.h: stack entries per lane in LDS, deeper ones in the global overflow area; >= FJ_STACK_LDS_MIN)
 #ifndef FJ_CANYHIT_MINB
 #define FJ_CANYHIT_MINB 4
 #endif

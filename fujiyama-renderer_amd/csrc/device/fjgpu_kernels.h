@@ -99,6 +99,11 @@ void set_anyhit_filter_off(long v);     // diagnostics: fjgpu_global_option("any
 void light_cone_validate_counts(double *verdicts, double *contradictions);
 // -DFJ_LIGHT_HULL_VALIDATE builds: the hull-settled pairs the any-hit walks have walked so far and how many of those walks found a hit; other builds: -1, -1
 void light_hull_validate_counts(double *verdicts, double *contradictions);
+// -DFJ_TRI_FILTER_VALIDATE builds: the filter's verdicts in the lean any-hit walk so far (current device) -- miss, hit, maybe --, the exact test's hits and
+// the verdicts it contradicted, in that order; other builds: -1 five times.  Reads only (debug_phase_stats prints and resets them).
+void tri_filter_validate_counts(double out[5]);
+// the constants THIS file's kernels were compiled with (fjgpu_build_config's names); false: no such name.  No device call.
+bool kernels_build_config(const char *name, double *value);
 void debug_phase_stats();     // FJ_PHASE_STATS builds: print and reset the any-hit walk's phase tallies (stderr)
 // threads of the largest persistent grid (sizes per-thread scratch such as the stack overflow area)
 size_t persistent_threads();

@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "fjgpu_types.h"
 #include "fjgpu_kernels.h"
@@ -471,6 +472,40 @@ void light_hull_validate_counts(double *verdicts, double *contradictions)
   unsigned long long c[2];
   if (hipMemcpyFromSymbol(c, HIP_SYMBOL(g_lighthull), sizeof(c)) == hipSuccess) { *verdicts = (double) c[0]; *contradictions = (double) c[1]; }
 #endif
+}
+
+void tri_filter_validate_counts(double out[5])
+{
+  for (int k = 0; k < 5; k++) out[k] = -1;
+#ifdef FJ_TRI_FILTER_VALIDATE
+  unsigned long long c[8];
+  if (hipMemcpyFromSymbol(c, HIP_SYMBOL(g_trifilter), sizeof(c)) == hipSuccess) { out[0] = (double) c[0]; out[1] = (double) c[1]; out[2] = (double) c[2]; out[3] = (double) c[4]; out[4] = (double) c[3]; }
+#endif
+}
+
+bool kernels_build_config(const char *name, double *value)
+{
+  static const struct { const char *name; double value; } table[] = {
+    {"stack_lds", FJ_STACK_LDS}, {"stack_lds_curves", FJ_STACK_LDS_CURVES}, {"stack_lds_anyhit", FJ_STACK_LDS_ANYHIT},
+    {"stack_lds_canyhit", FJ_STACK_LDS_CANYHIT}, {"stack_lds_min", FJ_STACK_LDS_MIN},
+#ifdef FJ_TRI_FILTER_VALIDATE
+    {"tri_filter_validate", 1},
+#else
+    {"tri_filter_validate", 0},
+#endif
+#ifdef FJ_LIGHT_CONE_VALIDATE
+    {"light_cone_validate", 1},
+#else
+    {"light_cone_validate", 0},
+#endif
+#ifdef FJ_LIGHT_HULL_VALIDATE
+    {"light_hull_validate", 1},
+#else
+    {"light_hull_validate", 0},
+#endif
+  };
+  for (const auto &t : table) if (!strcmp(name, t.name)) { *value = t.value; return true; }
+  return false;
 }
 
 void debug_phase_stats()

@@ -56,8 +56,12 @@ static_assert(sizeof(DNodeQ) == 64, "DNodeQ must be 64 bytes");
 #ifndef FJ_STACK_LDS_ANYHIT
 #define FJ_STACK_LDS_ANYHIT 12
 #endif
+// the any-hit walk of curve scenes (fjgpu_dev_anyhit_curves.h); >= FJ_STACK_LDS_MIN
+#ifndef FJ_STACK_LDS_CANYHIT
+#define FJ_STACK_LDS_CANYHIT 16
+#endif
 #ifndef FJ_STACK_LDS_MIN
-#define FJ_STACK_LDS_MIN 12          // smallest of the three (sizes the global overflow area)
+#define FJ_STACK_LDS_MIN 12          // smallest of them (sizes the global overflow area)
 #endif
 
 // ---- primitive set (one mesh or one curve set): its BLAS + attribute arrays

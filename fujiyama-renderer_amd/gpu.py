@@ -58,6 +58,7 @@ def lib():
         L.fjgpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.fjgpu_global_option.argtypes = [C.c_char_p, C.c_long]
         L.fjgpu_scene_query.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
+        L.fjgpu_build_config.argtypes = [C.c_char_p, C.POINTER(C.c_double)]
         L.fjgpu_dev_rccl_selftest.argtypes = [C.c_int, C.c_int]
         L.fjgpu_dev_sort_pairs.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double)]
         _lib = L
@@ -727,6 +728,13 @@ class TemporalDenoiser(object):
         self._prev = (view, aov, hist)
         self.frames += 1
         return res, info
+
+
+def build_config(name):
+    """what the loaded library was compiled with (fjgpu_build_config): "stack_lds*", "*_validate"; no device needed"""
+    v = C.c_double(0)
+    _check(lib().fjgpu_build_config(name.encode(), C.byref(v)))
+    return v.value
 
 
 def global_option(name, value):

@@ -507,8 +507,17 @@ int fjgpu_host_light_hulls(const fj_scene_desc *desc, int group, void *out_recor
  * -1 in any other build), "light_hull_rows" / "light_hull_records" (the same for the hull-cone table), "light_hull_verdicts" (pairs the hull
  * cones settled in the last render call with count_nodes on, else 0; a -DFJ_LIGHT_HULL_VALIDATE build: the settled pairs queued and walked
  * all the same since the library was loaded), "light_hull_contradictions" (that build: how many of those walks found a hit; -1 in any other
- * build).  Returns 0 or FJGPU_EINVAL. */
+ * build), "stack_lds_canyhit" (the LDS entries of k_shadow_anyhit_curves, beside the other four), "tri_filter_miss" / "tri_filter_hit" /
+ * "tri_filter_maybe" / "tri_filter_exact_hits" / "tri_filter_contradictions" (a -DFJ_TRI_FILTER_VALIDATE build: the verdicts of the lean
+ * any-hit walk's f32 triangle filter since the library was loaded, the hits of the exact test run behind every one of them, and the MISS / HIT
+ * verdicts the exact test contradicted; reading does not reset them; -1 in any other build).  Returns 0 or FJGPU_EINVAL. */
 int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value);
+
+/* What this library was compiled with; needs no device and no scene.  Names: "stack_lds", "stack_lds_curves", "stack_lds_anyhit",
+ * "stack_lds_canyhit", "stack_lds_min" (traversal stack entries per lane the walks keep in LDS: FJ_STACK_LDS*), "tri_filter_validate",
+ * "light_cone_validate", "light_hull_validate" (1: built with -DFJ_TRI_FILTER_VALIDATE / -DFJ_LIGHT_CONE_VALIDATE / -DFJ_LIGHT_HULL_VALIDATE,
+ * 0: not).  Returns 0, or FJGPU_EINVAL for an unknown name or a NULL argument. */
+int fjgpu_build_config(const char *name, double *value);
 
 /* Diagnostics: the host-side math that feeds geometry to the device (matrices,
  * RNG tables, sampler margins), exported so it can be pinned against the

@@ -57,6 +57,18 @@ def headline(asset_dir, *lines):
     return with_props(workloads.dragon(asset_dir, mesh="tiny", nlights=4, **SHAPE), *lines)
 
 
+# the headline with a second, smaller dragon in a group of its own: the floor's and the small dragon's shadow rays go to group1 (the dragon), the dragon's to group2
+TWO_GROUPS = ("SetProperty3 dragon_shader0 diffuse 0.6 0.3 0.2",
+              "NewObjectInstance dragon2 dragon_mesh",
+              "SetProperty3 dragon2 scale 0.3 0.3 0.3",
+              "SetProperty3 dragon2 translate -1.3 0 1.2",
+              "AssignShader dragon2 DEFAULT_SHADING_GROUP dragon_shader0",
+              "NewObjectGroup group2",
+              "AddObjectToGroup group2 dragon2",
+              "AssignObjectGroup dragon1 shadow_target group2",
+              "AssignObjectGroup dragon2 shadow_target group1")
+
+
 def group_box(text, group=0):
     """the reference box of the single-instance group (DGroup.sbounds: the instance's bounds + 1e-4, the statement of the scene builder)"""
     sp, rd = tg.prepare(text)
@@ -108,16 +120,7 @@ def test_dome_light_scene_small(asset_dir):
 def test_two_single_instance_groups_in_one_frame(asset_dir):
     """the floor's records name group1 (the dragon), the dragon's name group2 (a second, smaller dragon) and the small dragon's group1 again:
     waves whose 64 records straddle an outline hold records of different groups and take the box test, the others their group's cones"""
-    text = headline(asset_dir,
-                    "SetProperty3 dragon_shader0 diffuse 0.6 0.3 0.2",
-                    "NewObjectInstance dragon2 dragon_mesh",
-                    "SetProperty3 dragon2 scale 0.3 0.3 0.3",
-                    "SetProperty3 dragon2 translate -1.3 0 1.2",
-                    "AssignShader dragon2 DEFAULT_SHADING_GROUP dragon_shader0",
-                    "NewObjectGroup group2",
-                    "AddObjectToGroup group2 dragon2",
-                    "AssignObjectGroup dragon1 shadow_target group2",
-                    "AssignObjectGroup dragon2 shadow_target group1")
+    text = headline(asset_dir, *TWO_GROUPS)
     got, rows, records = both_settings(text)
     assert (rows, records) == (2, 8)
     assert got[1][1].shadow_traversed > 0

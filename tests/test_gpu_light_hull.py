@@ -14,7 +14,7 @@ import pytest
 import oracle_ffi
 import test_gpu_parity as tg
 from fujiyama_renderer_amd import gpu, workloads
-from test_gpu_light_cone import SHAPE, group_box, headline
+from test_gpu_light_cone import SHAPE, TWO_GROUPS, group_box, headline
 
 
 def both_settings(text):
@@ -102,16 +102,7 @@ def test_a_translucent_occluder(asset_dir):
 def test_two_single_instance_groups_in_one_frame(asset_dir):
     """floor -> group1 (the dragon), dragon -> group2 (a second, smaller dragon), small dragon -> group1: each group has its row; waves
     whose 64 records name different groups take the exact path"""
-    text = headline(asset_dir,
-                    "SetProperty3 dragon_shader0 diffuse 0.6 0.3 0.2",
-                    "NewObjectInstance dragon2 dragon_mesh",
-                    "SetProperty3 dragon2 scale 0.3 0.3 0.3",
-                    "SetProperty3 dragon2 translate -1.3 0 1.2",
-                    "AssignShader dragon2 DEFAULT_SHADING_GROUP dragon_shader0",
-                    "NewObjectGroup group2",
-                    "AddObjectToGroup group2 dragon2",
-                    "AssignObjectGroup dragon1 shadow_target group2",
-                    "AssignObjectGroup dragon2 shadow_target group1")
+    text = headline(asset_dir, *TWO_GROUPS)
     got, rows, records = both_settings(text)
     assert (rows, records) == (2, 8)
     assert got[1][1].shadow_traversed > 0

@@ -84,7 +84,7 @@ def gpu_trace(text, rays, group=0, count=False):
     if count:
         gs.set_option("count_nodes", 1)
     t, ids, uv, st = gs.trace(group, rays)
-    facts = {k: int(gs.query(k)) for k in ("stack_need", "blas_nodes", "stack_peak", "stack_peak_closest")}
+    facts = {k: int(gs.query(k)) for k in ("stack_need", "blas_nodes", "stack_peak", "stack_peak_closest", "closest_kernel")}
     gs.close()
     return t, ids, facts
 
@@ -94,6 +94,7 @@ def test_lds_constants_are_what_this_file_states(asset_dir):
     gs = gpu.Scene(sp)
     assert int(gs.query("stack_lds")) == STACK_LDS and int(gs.query("stack_lds_anyhit")) == STACK_LDS_ANYHIT
     assert int(gs.query("stack_lds_curves")) == STACK_LDS_CURVES and int(gs.query("stack_lds_min")) == min(STACK_LDS_ANYHIT, STACK_LDS)
+    assert int(gs.query("stack_lds_canyhit")) == STACK_LDS_CANYHIT
     assert int(gs.query("stack_peak")) == 0
     gs.close()
 
@@ -236,7 +237,8 @@ def render_counted(text, batch_tiles=0):
     osc.close()
     assert np.array_equal(fb, fb2) or float(tg.rel_err(fb, fb2).max()) <= 1e-6
     assert st.rays.as_dict() == rc.as_dict() == st2.rays.as_dict(), (st.rays.as_dict(), rc.as_dict())
-    assert float(tg.rel_err(fb, ref).max()) <= REL_TOL
+    facts["max_rel_err"] = float(tg.rel_err(fb, ref).max())
+    assert facts["max_rel_err"] <= REL_TOL, facts["max_rel_err"]
     facts["rays"] = rc.as_dict()
     return facts
 
@@ -298,7 +300,8 @@ def test_telescope_frames_overflow_the_lds_stack(how, walk, batch_tiles, tmp_pat
     and what does not:
       k_trace_closest_flat (32)           15: flat groups take host trees only, whose leaves hold an octave's triangles together
       k_shadow_trace (32)                 3 / 6: it visits the nearest child first and a translucent hit shortens the ray
-    Those two are asserted at the measured depth; their overflow indexing stays covered by the -DFJ_STACK_LDS=4 variant build."""
+    Those two are asserted at the measured depth here; their overflow rows are written and read back by the same frames in the stack4
+    variant build (4 entries in LDS in every walk), which tests/test_gpu_variant_builds.py runs."""
     shader, n_inst, opts, kernel, lean = FRAME_WALKS[walk]
     v, t = pm.telescope()
     path = pm.write_mesh(tmp_path, "telescope", v, t)
@@ -327,21 +330,27 @@ def test_telescope_frames_overflow_the_lds_stack(how, walk, batch_tiles, tmp_pat
     assert facts["stack_peak"] <= facts["stack_need"]
 
 
+def fur_telescope_text(directory, asset_dir):
+    """the fur scene of the workloads (48 x 32, 2 x 2 samples, two lights) with the ten largest octaves of the telescope, at a size of
+    0.5, in place of its mesh"""
+    from fujiyama_renderer_amd import workloads
+    v, t = pm.telescope(n=30)
+    v = (v.astype(np.float64) * (0.5 / pm.TELESCOPE_SCALE)).astype(np.float32)
+    path = pm.write_mesh(directory, "telescope_fur", v, t)
+    text = workloads.furry(asset_dir, res=(48, 32), spp=(2, 2), mesh="furball", nlights=2)
+    old = synth.ensure_assets(asset_dir, ("furball",))["furball"]
+    assert old in text
+    return text.replace(old, path)
+
+
 def test_fur_on_the_telescope(tmp_path, asset_dir):
     """the curve walks (k_shadow_anyhit_curves: 16 entries in LDS, the curve instantiation of k_trace_closest: 20): fur can only be
     grown on a mesh by CurveGeneratorProcedure, here on the ten largest octaves of the telescope at a size of 0.5 (the oracle's grid
     over the curves takes 2 s to build at this size and 14 s at 2.0).  Parity with the oracle, and the depth the walks reach:
     measured stack_need 38, closest-hit walk 16, any-hit walk 16 -- the last LDS entry, not beyond (at size 2.0: need 49, 15 and 19,
-    three rows of the overflow area).  So in the suite the curve walks' overflow indexing still rests on the -DFJ_STACK_LDS=4
-    variant build."""
-    from fujiyama_renderer_amd import workloads
-    v, t = pm.telescope(n=30)
-    v = (v.astype(np.float64) * (0.5 / pm.TELESCOPE_SCALE)).astype(np.float32)
-    path = pm.write_mesh(tmp_path, "telescope_fur", v, t)
-    text = workloads.furry(asset_dir, res=(48, 32), spp=(2, 2), mesh="furball", nlights=2)
-    old = synth.ensure_assets(asset_dir, ("furball",))["furball"]
-    assert old in text
-    facts = render_counted(text.replace(old, path))
+    three rows of the overflow area).  So the DEFAULT build's curve walks stay inside LDS here; their overflow rows are covered by this
+    scene in the stack4 variant build (4 entries in LDS), run by tests/test_gpu_variant_builds.py."""
+    facts = render_counted(fur_telescope_text(tmp_path, asset_dir))
     print("telescope fur", facts)
     assert facts["closest_kernel"] == 2 and facts["curve_anyhit"] == 1 and facts["rays"]["shadow"] > 0
     assert facts["stack_need"] > STACK_LDS_CURVES
