@@ -1348,6 +1348,42 @@ int fjgpu_dev_sort_pairs(int device, const uint32_t *keys, int n, int key_bits, 
   return 0;
 }
 
+int fjgpu_dev_slab32_batch(int device, int n, const double *rays, const double *grid, const uint32_t *words, void *out)
+{
+  if (n < 0 || (n > 0 && (!rays || !grid || !words || !out))) return fail(FJGPU_EINVAL, "bad slab32 batch call");
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return fail(FJGPU_ENODEV, "no such HIP device");
+  HIP_TRY(hipSetDevice(device));
+  if (n == 0) return 0;
+  DeviceBuffers M;
+  const double *d_rays = nullptr, *d_grid = nullptr;
+  const uint32_t *d_words = nullptr;
+  char *d_out = nullptr;
+  if (M.upload(rays, (size_t) n * 8, &d_rays) || M.upload(grid, (size_t) n * 6, &d_grid) || M.upload(words, (size_t) n * 3, &d_words) || M.alloc((size_t) n * 128, &d_out))
+    return fail(FJGPU_ENOMEM, "device allocation failed for the slab32 batch");
+  if (launch_slab32_batch(nullptr, (uint32_t) n, d_rays, d_grid, d_words, d_out)) return fail(FJGPU_ENODEV, "the slab32 batch launch failed");
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipMemcpy(out, d_out, (size_t) n * 128, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int fjgpu_dev_quantize_nodes(int device, int n, const void *nodes, const double *origin, const double *cell, void *out)
+{
+  if (n < 0 || !origin || !cell || (n > 0 && (!nodes || !out))) return fail(FJGPU_EINVAL, "bad quantize call");
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return fail(FJGPU_ENODEV, "no such HIP device");
+  HIP_TRY(hipSetDevice(device));
+  if (n == 0) return 0;
+  DeviceBuffers M;
+  const DNode *d_nodes = nullptr;
+  DNodeQ *d_out = nullptr;
+  if (M.upload((const DNode *) nodes, (size_t) n, &d_nodes) || M.alloc((size_t) n, &d_out)) return fail(FJGPU_ENOMEM, "device allocation failed for the quantiser");
+  if (launch_quantize_nodes(nullptr, d_nodes, (uint32_t) n, origin, cell, d_out)) return fail(FJGPU_ENODEV, "the quantiser's launch failed");
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipMemcpy(out, d_out, sizeof(DNodeQ) * (size_t) n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value)
 {
   if (!scene || !name) return fail(FJGPU_EINVAL, "bad option call");

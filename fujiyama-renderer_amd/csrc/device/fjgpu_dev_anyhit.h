@@ -20,7 +20,7 @@
 // triangle per lane and execution, so lanes with 1 and 4 triangles do not wait for each other.
 //
 // Box tests are the conservative sign-aware f32 slab test on the quantised 64-byte nodes
-// (slab32q_test, fjgpu_dev_math.h).
+// (slab32q_test, fjgpu_slab32.h).
 //
 // Entry.  The light loop has already tested the (single) instance box of single-instance
 // shadow groups and writes ~instance into the queue entry: the walk reads one flat record

@@ -5,7 +5,8 @@
 #define FJGPU_DEV_MATH_H
 
 // ------------------------------------------------------------------ vectors
-struct V3 { double x, y, z; };
+// V3, fj_v2f, the f64 slab test and the f32 slab tests (slab32*, f32_below / f32_above, the quantiser): one source for device and host
+#include "fjgpu_slab32.h"
 __device__ __forceinline__ V3 mk(double x, double y, double z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
 __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ V3 operator-(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -26,7 +27,6 @@ __device__ __forceinline__ V3 normalize(V3 a)
 // stack also waits for the node or triangle fetch in flight.  These arrays are global memory.
 #define FJ_GLOBAL __attribute__((address_space(1)))
 typedef float fj_v4f __attribute__((ext_vector_type(4)));
-typedef float fj_v2f __attribute__((ext_vector_type(2)));
 typedef uint32_t fj_v4u __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ V3 ld3(const double *p) { return mk(p[0], p[1], p[2]); }
@@ -49,21 +49,6 @@ __device__ __forceinline__ V3 xvector(const double *m, V3 v)
 
 __device__ __forceinline__ double clampd(double x, double a, double b) { return x < a ? a : (x > b ? b : x); }
 
-// ------------------------------------------------------------ culling tests
-// Conservative slab test (culling only).  NaN from 0 * inf is ignored by
-// fmin/fmax, which return the non-NaN operand.
-__device__ __forceinline__ bool slab(const double bmin[3], const double bmax[3], V3 o, V3 inv,
-    double tmin, double tmax, double *tnear)
-{
-  const double x0 = (bmin[0] - o.x) * inv.x, x1 = (bmax[0] - o.x) * inv.x;
-  const double y0 = (bmin[1] - o.y) * inv.y, y1 = (bmax[1] - o.y) * inv.y;
-  const double z0 = (bmin[2] - o.z) * inv.z, z1 = (bmax[2] - o.z) * inv.z;
-  const double tn = fmax(fmax(fmin(x0, x1), fmin(y0, y1)), fmax(fmin(z0, z1), tmin));
-  const double tf = fmin(fmin(fmax(x0, x1), fmax(y0, y1)), fmin(fmax(z0, z1), tmax));
-  *tnear = tn;
-  return tn <= tf;
-}
-
 // the f64 test on a DNode child box ((min, max) pairs); kept for validation builds
 __device__ __forceinline__ bool slab_f32box(fj_v2f px, fj_v2f py, fj_v2f pz, V3 o, V3 inv,
     double tmin, double tmax, double *tnear)
@@ -72,177 +57,6 @@ __device__ __forceinline__ bool slab_f32box(fj_v2f px, fj_v2f py, fj_v2f pz, V3 
   const double mx[3] = {(double) px.y, (double) py.y, (double) pz.y};
   return slab(mn, mx, o, inv, tmin, tmax, tnear);
 }
-
-// ---- conservative f32 slab test on the BLAS node boxes (culling only).
-// DNode stores a child's box as three (min, max) pairs, so one packed fma yields both plane
-// distances of an axis.  Per (ray, instance) and axis a the entry code keeps
-//   i = (float)(1/od_a),  o = (float)(oo_a/od_a),  e = 3.6e-7 (Bmax_a |i| + |o|),
-//   l = -(o + e),  h = e - o,     Bmax_a >= |any box coordinate| of the primitive set.
-// For a box plane b (f32) the exact distance is t = (b - oo_a)/od_a.  t~ = fmaf(b, i, -o)
-// differs from t by at most |b/od| 2^-24 (rounding of i) + |oo/od| 2^-24 (rounding of o; the
-// f64 reciprocal and product before it are good to 2^-49) + |t~| 2^-24 (the fma's rounding)
-// <= 2^-23 (Bmax |i| + |o|)(1 + 2^-18) =: E.  e is 3 E; folding it into the addend costs
-// another 2^-24 |o + e|, so fmaf(b, i, l) <= t - E' and fmaf(b, i, h) >= t + E' with E' > E:
-// [min over the two planes of the l-variant, max of the h-variant] contains the exact slab
-// interval, and the f64 interval of slab_f32box (own error ~2^-52).  Whatever the f64 test
-// accepts this one accepts: it can only cull less.  An axis whose e is not a finite number
-// below 1e30 (direction component zero or denormal: 1/od = inf) gets i = 0, l = -1e30,
-// h = 1e30: interval [-1e30, 1e30], it never culls.  With e < 1e30 every product is finite or
-// an infinity of one sign: no NaN can arise (box coordinates are finite).
-// one axis: t_lo = fmaf(b, i, l), t_hi = fmaf(b, i, h).  (Plain values, no pointers into a
-// struct: the compiler kept a by-reference Slab32 in scratch memory.)
-struct Slab32Axis { float i, l, h; };
-struct Slab32 { Slab32Axis x, y, z; };
-
-// inv = 1/od good to 2^-49 (filter_rcp) or exact
-__device__ __forceinline__ Slab32Axis slab32_axis(double inv, double oo, double bmax_abs)
-{
-  const float i = (float) inv, o = (float) (oo * inv);
-  // (node boxes are rounded outward from the f64 bounds by up to 2 ulp: the factor covers 8)
-  const float e = 3.6e-7f * ((float) bmax_abs * 1.000001f * fabsf(i) + fabsf(o));
-  const bool ok = e < 1e30f;
-  Slab32Axis a;
-  a.i = ok ? i : 0.f;
-  a.l = ok ? -(o + e) : -1e30f;
-  a.h = ok ? e - o : 1e30f;
-  return a;
-}
-
-// bounds = {min xyz, max xyz} of the primitive set (every node box lies inside)
-__device__ __forceinline__ Slab32 slab32_setup(V3 oo, V3 inv, const double *bounds)
-{
-  Slab32 s;
-  s.x = slab32_axis(inv.x, oo.x, fmax(fabs(bounds[0]), fabs(bounds[3])));
-  s.y = slab32_axis(inv.y, oo.y, fmax(fabs(bounds[1]), fabs(bounds[4])));
-  s.z = slab32_axis(inv.z, oo.z, fmax(fabs(bounds[2]), fabs(bounds[5])));
-  return s;
-}
-
-// The same constants for QUANTISED boxes (DNodeQ): a plane is g0 + q cell with q an integer in
-// [0, 65535], so t = (g0 + q cell - oo)/od = q (cell/od) + (g0 - oo)/od, and
-//   t~ = fmaf((float) q, A, B),  A = (float)(cell/od),  B = (float)((g0 - oo)/od)
-// is off by at most 2^-23 (65535 |A| + |B|)(1 + 2^-18) (roundings of A, of B, of the fma; (float) q
-// is exact).  i = A, l = B - e, h = B + e with e three times that bound, as above.
-//
-// FJ_SLAB_PERM (default): the integer reaches the fma WITHOUT a conversion instruction.  A byte permute
-// (v_perm_b32) drops the 16-bit coordinate into the mantissa of 2^23: as_float(0x4B000000 | q) IS the
-// number 8388608 + q, exactly.  The fma then computes (8388608 + q) A + (c - 8388608 A) -- product and sum
-// exact, ONE rounding of the result, which has the magnitude of t again -- so all that is new is the
-// rounding of the shifted addend c' = fmaf(-8388608, A, c): half an ulp of a number of magnitude <= 8388608 |A| + |c|,
-// i.e. <= |A| / 2 + 2^-24 |c| (the second term is inside e already).  l' and h' are moved outward by FJ_SLAB_PERM_PAD |A|
-// (0.51) for it: the box grows by half a grid cell (of 65536 per axis).  Per child and axis: two permutes instead of a
-// rotate and two SDWA conversions.  (Measured on C3 with a pad of 2 cells: 1 % more boxes pass, +2.4 % nodes, +10 % triangle
-// tests -- leaf boxes are only ~80 cells wide; validated: 48.5 G box tests, 0 lost, profiles/r03_anyhit_wide8_and_perm.txt.)
-#ifndef FJ_SLAB_PERM
-#define FJ_SLAB_PERM 1
-#endif
-#ifndef FJ_SLAB_PERM_PAD
-#define FJ_SLAB_PERM_PAD .51f
-#endif
-__device__ __forceinline__ Slab32Axis slab32q_axis(double inv, double oo, double g0, double cell)
-{
-  const float A = (float) (cell * inv), B = (float) ((g0 - oo) * inv);
-  const float e = 3.6e-7f * (65535.f * 1.000001f * fabsf(A) + fabsf(B));
-  const bool ok = e < 1e30f;
-  Slab32Axis a;
-  a.i = ok ? A : 0.f;
-#if FJ_SLAB_PERM
-  a.l = ok ? fmaf(-8388608.f, A, B - e) - FJ_SLAB_PERM_PAD * fabsf(A) : -1e30f;
-  a.h = ok ? fmaf(-8388608.f, A, B + e) + FJ_SLAB_PERM_PAD * fabsf(A) : 1e30f;
-#else
-  a.l = ok ? B - e : -1e30f;
-  a.h = ok ? B + e : 1e30f;
-#endif
-  return a;
-}
-__device__ __forceinline__ Slab32 slab32q_setup(V3 oo, V3 inv, const double *g0, const double *cell)
-{
-  Slab32 s;
-  s.x = slab32q_axis(inv.x, oo.x, g0[0], cell[0]);
-  s.y = slab32q_axis(inv.y, oo.y, g0[1], cell[1]);
-  s.z = slab32q_axis(inv.z, oo.z, g0[2], cell[2]);
-  return s;
-}
-// (min, max) pair of grid coordinates packed in one 32-bit word -> two floats
-__device__ __forceinline__ fj_v2f unpack_q(uint32_t w) { fj_v2f p; p.x = (float) (w & 0xffffu); p.y = (float) (w >> 16); return p; }
-
-// px py pz = the (min, max) pairs of a child box; tmin32 <= tmin and tmax32 >= tmax of the ray.
-// *tnear = conservative entry distance (an ordering key for the closest-hit walk).
-__device__ __forceinline__ bool slab32_test(fj_v2f px, fj_v2f py, fj_v2f pz, const Slab32 s, float tmin32, float tmax32, float *tnear)
-{
-  const fj_v2f lx = __builtin_elementwise_fma(px, (fj_v2f) (s.x.i), (fj_v2f) (s.x.l));
-  const fj_v2f hx = __builtin_elementwise_fma(px, (fj_v2f) (s.x.i), (fj_v2f) (s.x.h));
-  const fj_v2f ly = __builtin_elementwise_fma(py, (fj_v2f) (s.y.i), (fj_v2f) (s.y.l));
-  const fj_v2f hy = __builtin_elementwise_fma(py, (fj_v2f) (s.y.i), (fj_v2f) (s.y.h));
-  const fj_v2f lz = __builtin_elementwise_fma(pz, (fj_v2f) (s.z.i), (fj_v2f) (s.z.l));
-  const fj_v2f hz = __builtin_elementwise_fma(pz, (fj_v2f) (s.z.i), (fj_v2f) (s.z.h));
-  const float tn = fmaxf(fmaxf(fmaxf(fminf(lx.x, lx.y), fminf(ly.x, ly.y)), fminf(lz.x, lz.y)), tmin32);
-  const float tf = fminf(fminf(fminf(fmaxf(hx.x, hx.y), fmaxf(hy.x, hy.y)), fmaxf(hz.x, hz.y)), tmax32);
-  *tnear = tn;
-  return tn <= tf;
-}
-// The same test on a QUANTISED box with the direction signs of the ray used up front: wx wy wz are the
-// (min, max) words of one child; sh* (slab32_shift) say which half of a word is the NEAR plane on that
-// axis -- the low one unless the ray runs towards smaller coordinates.  With the near plane in the first
-// and the far plane in the second element, one packed fma per axis yields (entry, exit) directly --
-// fma(b, i, l) is monotonic in b, hence min(fma(min, i, l), fma(max, i, l)) IS fma(near, i, l) and
-// likewise for the exit side: the same numbers as slab32_test, 4 instead of 6 instructions per axis.
-//   FJ_SLAB_PERM 1: sh = the v_perm_b32 selector that builds as_float(0x4B000000 | near half) -- result bytes 3, 2 =
-//                   bytes 3, 2 of the constant (selector values 7, 6), bytes 1, 0 = the word's (1, 0) or (3, 2); the
-//                   far half's selector is sh ^ 0x0202
-//   FJ_SLAB_PERM 0: sh = 16 or 0, the word is rotated (v_alignbit_b32) and converted (2 SDWA cvt)
-#if FJ_SLAB_PERM
-__device__ __forceinline__ uint32_t slab32_shift(float i) { return 0x07060100u ^ ((__float_as_uint(i) >> 31) * 0x0202u); }
-__device__ __forceinline__ fj_v2f slab32q_planes(uint32_t w, uint32_t sh)
-{
-  fj_v2f p;
-  p.x = __uint_as_float(__builtin_amdgcn_perm(0x4B000000u, w, sh));
-  p.y = __uint_as_float(__builtin_amdgcn_perm(0x4B000000u, w, sh ^ 0x0202u));
-  return p;
-}
-#else
-__device__ __forceinline__ uint32_t slab32_shift(float i) { return (__float_as_uint(i) >> 31) << 4; }
-__device__ __forceinline__ fj_v2f slab32q_planes(uint32_t w, uint32_t sh) { return unpack_q(__builtin_amdgcn_alignbit(w, w, sh)); }
-#endif
-__device__ __forceinline__ bool slab32q_test(uint32_t wx, uint32_t wy, uint32_t wz, const Slab32 s, uint32_t shx, uint32_t shy, uint32_t shz,
-    float tmin32, float tmax32, float *tnear = nullptr)
-{
-  const fj_v2f px = slab32q_planes(wx, shx);
-  const fj_v2f py = slab32q_planes(wy, shy);
-  const fj_v2f pz = slab32q_planes(wz, shz);
-  fj_v2f cx, cy, cz;
-  cx.x = s.x.l; cx.y = s.x.h; cy.x = s.y.l; cy.y = s.y.h; cz.x = s.z.l; cz.y = s.z.h;
-  const fj_v2f tx = __builtin_elementwise_fma(px, (fj_v2f) (s.x.i), cx);
-  const fj_v2f ty = __builtin_elementwise_fma(py, (fj_v2f) (s.y.i), cy);
-  const fj_v2f tz = __builtin_elementwise_fma(pz, (fj_v2f) (s.z.i), cz);
-  const float tn = fmaxf(fmaxf(fmaxf(tx.x, ty.x), tz.x), tmin32);
-  const float tf = fminf(fminf(fminf(tx.y, ty.y), tz.y), tmax32);
-  if (tnear) *tnear = tn;
-  return tn <= tf;
-}
-// the same with the slab constants held the way the packed fma wants them: (l, h) of an axis as ONE two-float value (a register pair: built
-// per test from two scalars it cost the any-hit walk ten moves per iteration), the slope as a scalar (broadcast by the instruction's op_sel)
-struct Slab32P { float ix, iy, iz; fj_v2f lhx, lhy, lhz; };
-__device__ __forceinline__ Slab32P slab32p(const Slab32 s)
-{
-  Slab32P p;
-  p.ix = s.x.i; p.iy = s.y.i; p.iz = s.z.i;
-  p.lhx.x = s.x.l; p.lhx.y = s.x.h; p.lhy.x = s.y.l; p.lhy.y = s.y.h; p.lhz.x = s.z.l; p.lhz.y = s.z.h;
-  return p;
-}
-__device__ __forceinline__ bool slab32q_test(uint32_t wx, uint32_t wy, uint32_t wz, const Slab32P s, uint32_t shx, uint32_t shy, uint32_t shz,
-    float tmin32, float tmax32)
-{
-  const fj_v2f tx = __builtin_elementwise_fma(slab32q_planes(wx, shx), (fj_v2f) (s.ix), s.lhx);
-  const fj_v2f ty = __builtin_elementwise_fma(slab32q_planes(wy, shy), (fj_v2f) (s.iy), s.lhy);
-  const fj_v2f tz = __builtin_elementwise_fma(slab32q_planes(wz, shz), (fj_v2f) (s.iz), s.lhz);
-  const float tn = fmaxf(fmaxf(fmaxf(tx.x, ty.x), tz.x), tmin32);
-  const float tf = fminf(fminf(fminf(tx.y, ty.y), tz.y), tmax32);
-  return tn <= tf;
-}
-// f32 bounds of an f64 ray range: down / up to the neighbouring float
-__device__ __forceinline__ float f32_below(double x) { const float f = (float) x; return (double) f <= x ? f : nextafterf(f, -INFINITY); }
-__device__ __forceinline__ float f32_above(double x) { const float f = (float) x; return (double) f >= x ? f : nextafterf(f, INFINITY); }
 
 // Reference quirk kept for identical results: BoxRayIntersect (src/fj_box.cc:73-138)
 // branches on `dir >= 0`, which is true for -0.0, and then divides by -0.0: the

@@ -90,6 +90,8 @@ int launch_shadow_cull(hipStream_t st, const DScene &S, const ShadowParams &sp, 
 int launch_shadow_trace(hipStream_t st, const DScene &S, const DShadowRay *squeue, float *s_accum, DCounters *cnt, int count_events);
 // the quantised node array of the lean any-hit walk from the f32 one (same indices)
 int launch_quantize_nodes(hipStream_t st, const DNode *nodes, uint32_t n, const double *origin, const double *cell, DNodeQ *out);
+// diagnostics: n (ray, box) pairs through the walks' slab-test statements, one 128-byte Slab32Probe record each (fjgpu_slab32.h)
+int launch_slab32_batch(hipStream_t st, uint32_t n, const double *rays, const double *grid, const uint32_t *words, void *out);
 // multi-GPU frame: pack a device's tiles (d_rects [n][4] = xmin ymin xmax ymax) into a slab of
 // tile_px pixels per tile, or scatter such a slab into the framebuffer (unpack)
 int launch_move_tiles(hipStream_t st, bool unpack, float *fb, int xres, const int32_t *d_rects, int n_tiles, int tile_px, float *slab);

@@ -6,6 +6,7 @@
 //
 // Kernel map -- one translation unit, the device code lives in headers:
 //   fjgpu_dev_math.h      vectors, slab / exact box tests, transforms at a time, tri_ray
+//   fjgpu_slab32.h        the conservative slab tests (f64, f32 boxes, quantised boxes) and the node quantiser's arithmetic: also built for the host
 //   fjgpu_dev_curve.h     curve_ray (Bezier ribbons) + the reference grid's cell listing
 //   fjgpu_dev_traverse.h  traverse_persistent, k_trace_closest   (Accelerator::Intersect:
 //                         instance loop -> 4-wide BLAS, LDS stack -> FP64 Moller-Trumbore)
@@ -116,7 +117,7 @@ __global__ void __launch_bounds__(BLOCK) k_move_tiles(float4 *fb, int xres, cons
 }
 
 // ------------------------------------------------------- k_quantize_nodes
-// DNode -> DNodeQ (fjgpu_types.h): child boxes outward onto the 65536^3 grid origin + q * cell.
+// DNode -> DNodeQ (fjgpu_types.h): child boxes outward onto the 65536^3 grid origin + q * cell (slab32_quantize_axis, fjgpu_slab32.h).
 // floor / ceil in f64, then checked against the decoded plane and stepped outward if a rounding
 // went the wrong way: the decoded box contains the f32 box wherever that box lies inside the
 // grid (coordinates clamp to [0, 65535]; the grid spans the primitive set's PADDED bounds, and a
@@ -135,18 +136,29 @@ __global__ void __launch_bounds__(BLOCK) k_quantize_nodes(const DNode *nodes, ui
     q.child[k] = nd.child[k];
     for (int a = 0; a < 3; a++) {
       const double lo = (double) nd.box[k][2 * a], hi = (double) nd.box[k][2 * a + 1];
-      double ql = floor((lo - o[a]) / c[a]), qh = ceil((hi - o[a]) / c[a]);
-      if (!(ql >= 0)) ql = 0;                    // (also the empty slots' +-FLT_MAX / NaN)
-      if (!(qh <= 65535)) qh = 65535;
-      if (!(qh >= 0)) qh = 0;
-      if (!(ql <= 65535)) ql = 65535;
-      if (o[a] + ql * c[a] > lo && ql > 0) ql -= 1;
-      if (o[a] + qh * c[a] < hi && qh < 65535) qh += 1;
-      q.q[k][2 * a] = (uint16_t) ql;
-      q.q[k][2 * a + 1] = (uint16_t) qh;
+      slab32_quantize_axis(lo, hi, o[a], c[a], &q.q[k][2 * a], &q.q[k][2 * a + 1]);
     }
   }
   out[i] = q;
+}
+
+// ------------------------------------------------------- k_slab32_batch
+// Diagnostics (fjgpu_dev_slab32_batch): one (ray, box) pair per lane through the walks' own entry statements -- filter_rcp of the direction,
+// slab32q_setup, slab32_shift, both slab32q_test overloads, slab32_setup / slab32_test -- with every constant written out (slab32_probe,
+// fjgpu_slab32.h: the host tool runs the same function on the reciprocals this kernel returns).
+//   rays [n][8]: o xyz, d xyz, tmin, tmax;   grid [n][6]: g0 xyz, cell xyz;   words [n][3]
+__global__ void __launch_bounds__(BLOCK) k_slab32_batch(uint32_t n, const double *rays, const double *grid, const uint32_t *words, Slab32Probe *out)
+{
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  double r[8], g[6];
+  for (int k = 0; k < 8; k++) r[k] = rays[(size_t) i * 8 + k];
+  for (int k = 0; k < 6; k++) g[k] = grid[(size_t) i * 6 + k];
+  const uint32_t w[3] = {words[(size_t) i * 3], words[(size_t) i * 3 + 1], words[(size_t) i * 3 + 2]};
+  r[3] = filter_rcp(r[3]); r[4] = filter_rcp(r[4]); r[5] = filter_rcp(r[5]);
+  Slab32Probe p;
+  slab32_probe(r, g, w, &p);
+  out[i] = p;
 }
 
 // ----------------------------------------------------------- host launchers
@@ -442,6 +454,14 @@ int launch_quantize_nodes(hipStream_t st, const DNode *nodes, uint32_t n, const 
   return 0;
 }
 
+int launch_slab32_batch(hipStream_t st, uint32_t n, const double *rays, const double *grid, const uint32_t *words, void *out)
+{
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_slab32_batch, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, n, rays, grid, words, (Slab32Probe *) out);
+  LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_move_tiles(hipStream_t st, bool unpack, float *fb, int xres, const int32_t *d_rects, int n_tiles, int tile_px, float *slab)
 {
   // (the tile index is grid.y, at most 65535 per launch: more tiles go in several launches)
@@ -488,6 +508,7 @@ bool kernels_build_config(const char *name, double *value)
   static const struct { const char *name; double value; } table[] = {
     {"stack_lds", FJ_STACK_LDS}, {"stack_lds_curves", FJ_STACK_LDS_CURVES}, {"stack_lds_anyhit", FJ_STACK_LDS_ANYHIT},
     {"stack_lds_canyhit", FJ_STACK_LDS_CANYHIT}, {"stack_lds_min", FJ_STACK_LDS_MIN},
+    {"slab_perm", FJ_SLAB_PERM},
 #ifdef FJ_TRI_FILTER_VALIDATE
     {"tri_filter_validate", 1},
 #else

@@ -61,6 +61,8 @@ def lib():
         L.fjgpu_build_config.argtypes = [C.c_char_p, C.POINTER(C.c_double)]
         L.fjgpu_dev_rccl_selftest.argtypes = [C.c_int, C.c_int]
         L.fjgpu_dev_sort_pairs.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+        L.fjgpu_dev_slab32_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fjgpu_dev_quantize_nodes.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -760,6 +762,33 @@ def sort_pairs(keys, key_bits, device=0, repeats=1):
     _check(lib().fjgpu_dev_sort_pairs(device, keys.ctypes.data_as(C.c_void_p), int(keys.size), int(key_bits),
                                       out.ctypes.data_as(C.c_void_p), perm.ctypes.data_as(C.c_void_p), int(repeats), C.byref(ms)))
     return out, perm, ms.value
+
+
+def slab32_batch(rays, grid, words, device=0):
+    """the walks' slab tests on their own (include/fjgpu.h: fjgpu_dev_slab32_batch): rays [n, 8] (o, d, tmin, tmax), grid [n, 6], words [n, 3]
+    -> [n] 128-byte records as uint8 [n, 128] (Slab32Probe of csrc/device/fjgpu_slab32.h)"""
+    rays = np.ascontiguousarray(rays, dtype=np.float64)
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    n = int(rays.shape[0])
+    assert rays.shape == (n, 8) and grid.shape == (n, 6) and words.shape == (n, 3)
+    out = np.zeros((n, 128), np.uint8)
+    _check(lib().fjgpu_dev_slab32_batch(device, n, rays.ctypes.data_as(C.c_void_p), grid.ctypes.data_as(C.c_void_p),
+                                        words.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def quantize_nodes(nodes, origin, cell, device=0):
+    """k_quantize_nodes on its own (include/fjgpu.h: fjgpu_dev_quantize_nodes): nodes = [n] 128-byte DNode records (any dtype of that size)
+    -> uint8 [n, 64] (DNodeQ records)"""
+    nodes = np.ascontiguousarray(nodes)
+    assert nodes.dtype.itemsize == 128 and nodes.ndim == 1
+    origin = np.ascontiguousarray(origin, dtype=np.float64)
+    cell = np.ascontiguousarray(cell, dtype=np.float64)
+    out = np.zeros((len(nodes), 64), np.uint8)
+    _check(lib().fjgpu_dev_quantize_nodes(device, int(len(nodes)), nodes.ctypes.data_as(C.c_void_p), origin.ctypes.data_as(C.c_void_p),
+                                          cell.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def tile_rect(render, tile_id):

@@ -540,6 +540,18 @@ int fjgpu_dev_rccl_selftest(int device, int n_floats);
  * sort_ms (may be NULL): the fastest of `repeats` device-side runs, HIP events around the sort's launches alone. */
 int fjgpu_dev_sort_pairs(int device, const uint32_t *keys, int n, int key_bits, uint32_t *keys_out, uint32_t *perm, int repeats, double *sort_ms);
 
+/* Diagnostics: the BLAS walks' conservative slab tests on their own (csrc/device/fjgpu_slab32.h).  n (ray, box) pairs of HOST arrays run
+ * through the statements the walks compile -- filter_rcp of the direction, slab32q_setup, slab32_shift, both slab32q_test overloads on the
+ * quantised box, slab32_setup / slab32_test on the same box decoded to f32 planes -- one pair per lane.
+ *   rays [n][8]: origin xyz, direction xyz, tmin, tmax;  grid [n][6]: grid origin xyz, cell xyz;  words [n][3]: (min, max) words of x, y, z
+ *   out [n] records of 128 bytes (Slab32Probe): double inv[3]; float q[9] (i, l, h of x, y, z, quantised form); float f[9] (f32 form);
+ *   float tnear_q, tnear_f; uint32 verdict (bit 0 slab32q_test, bit 1 its packed overload, bit 2 slab32_test); uint32 sh[3]; uint32 pad[2] */
+int fjgpu_dev_slab32_batch(int device, int n, const double *rays, const double *grid, const uint32_t *words, void *out);
+
+/* Diagnostics: k_quantize_nodes on its own: n BLAS nodes (128-byte DNode records, HOST array) onto the grid origin + q * cell;
+ * out [n] 64-byte DNodeQ records. */
+int fjgpu_dev_quantize_nodes(int device, int n, const void *nodes, const double *origin, const double *cell, void *out);
+
 /* Human-readable message for the last error on this thread. */
 const char *fjgpu_last_error(void);
 
