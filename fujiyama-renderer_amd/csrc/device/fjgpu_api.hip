@@ -1184,6 +1184,53 @@ int fjgpu_host_light_hulls(const fj_scene_desc *desc, int group, void *out_recor
   return (int) nl;
 }
 
+int fjgpu_host_curve_blas(const fj_scene_desc *desc, int curve_set, int32_t *out_curve, float *out_capsule, int32_t *out_depth,
+                          float *out_box, int cap, int32_t *out_grid_n, double *out_grid_cell, double *out_bounds)
+{
+  if (!desc || curve_set < 0 || curve_set >= desc->n_curves) return fail(FJGPU_EINVAL, "bad curve-BLAS query");
+  fjgpu::HostPrimSet ps;
+  std::string err;
+  const int e = fjgpu::BuildCurveSet(desc->curves[curve_set], &ps, &err);
+  if (e) return fail(e, err);
+  const int n = ps.n_prims;
+  for (int k = 0; k < 3; k++) {
+    if (out_grid_n) out_grid_n[k] = ps.grid_n[k];
+    if (out_grid_cell) out_grid_cell[k] = ps.grid_cell[k];
+  }
+  if (out_bounds) std::memcpy(out_bounds, ps.bounds, sizeof(ps.bounds));
+  for (int s = 0; s < n && s < cap; s++) {
+    if (out_curve) out_curve[s] = (int32_t) ps.prim_ids[s];
+    if (out_capsule) std::memcpy(out_capsule + 7 * (size_t) s, &ps.curve_capsule[(size_t) s * 8], 7 * sizeof(float));
+    if (out_depth) out_depth[s] = ps.curve_depth[s];
+  }
+  if (out_box && n > 0) {
+    if (ps.root & FJ_LEAF_FLAG) {
+      if (cap > 0) for (int k = 0; k < 6; k++) out_box[k] = (float) ps.bounds[k];
+    } else {
+      std::vector<char> seen((size_t) n, 0);
+      std::vector<uint32_t> todo(1, ps.root);          // (from the root: the node storage is handed out in chunks, not all of it is used)
+      while (!todo.empty()) {
+        const uint32_t at = todo.back();
+        todo.pop_back();
+        if (at >= ps.nodes.size()) return fail(FJGPU_EINVAL, "curve-BLAS query: node index out of range");
+        const DNode &nd = ps.nodes.data()[at];
+        for (int k = 0; k < 4; k++) {
+          const uint32_t c = nd.child[k];
+          if (c == FJ_NO_CHILD) continue;
+          if (!(c & FJ_LEAF_FLAG)) { todo.push_back(c); continue; }
+          const uint32_t first = (c & ~FJ_LEAF_FLAG) >> 3, count = (c & 7u) + 1;
+          for (uint32_t s = first; s < first + count && s < (uint32_t) n; s++) {
+            seen[s] = 1;
+            if ((int) s < cap) for (int a = 0; a < 3; a++) { out_box[6 * (size_t) s + a] = nd.box[k][2 * a]; out_box[6 * (size_t) s + 3 + a] = nd.box[k][2 * a + 1]; }
+          }
+        }
+      }
+      for (int s = 0; s < n; s++) if (!seen[s]) return fail(FJGPU_EINVAL, "curve-BLAS query: a slot has no leaf");
+    }
+  }
+  return n;
+}
+
 int fjgpu_build_config(const char *name, double *value)
 {
   if (!name || !value) return fail(FJGPU_EINVAL, "bad build_config call");

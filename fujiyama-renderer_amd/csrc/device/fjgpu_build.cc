@@ -536,7 +536,6 @@ int build_mesh(const fj_mesh_desc &m, HostPrimSet *ps, std::string *err, bool de
 
 }  // namespace
 
-int BuildCurveSet(const fj_curve_desc &c, HostPrimSet *ps, std::string *err);   // fjgpu_curve_build.cc
 
 // Instance level of one group (the reference's BVHAccelerator over ObjectInstances,
 // src/fj_bvh_accelerator.cc:79-107,253-334).  The TOPOLOGY is the reference's own -- sort the range

@@ -83,6 +83,9 @@ void BuildGroupNodes(const std::vector<DInstance> &instances, const std::vector<
 // returns 0 or a negative FJGPU_E* code with *err set
 int BuildHostScene(const fj_scene_desc *desc, HostScene *out, std::string *err, bool device_mesh_build = false);
 
+// BLAS, capsules and payload of one curve set (fjgpu_curve_build.cc); BuildHostScene calls it per set
+int BuildCurveSet(const fj_curve_desc &c, HostPrimSet *ps, std::string *err);
+
 // reference-exact host math used while flattening (fjgpu_xform.cc)
 void MakeTransform(const fj_xform_desc &x, double time, double M[16], double Minv[16]);
 void TransformBounds(const double M[16], const double in[6], double out[6]);

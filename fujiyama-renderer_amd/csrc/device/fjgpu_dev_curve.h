@@ -270,17 +270,35 @@ __device__ bool curve_ray(const FJ_GLOBAL double *cpw, const FJ_GLOBAL double *v
 // control points and of the four points moved by that velocity (box_bezier3, N_STEPS = 1).
 // Inner levels are pruned with the hull of both polygons widened by 1e-12 (relative): the
 // leaf's "cp + (end - cp)" differs from "end" by rounding only.
-__device__ bool curve_listed_in_cell_of_moving(const DPrimSet *P, const FJ_GLOBAL double *cpw, const FJ_GLOBAL double *velw, V3 hitp)
+// The cells whose box (get_grid_cell, :334-343; Box::ContainsPoint is inclusive) holds the hit point: per axis the cell floor() names
+// and, where the point lies ON one of its planes -- or, by the rounding of the division, an ulp beyond it -- the neighbour as well.
+// The reference's walk tests the hit against every cell it passes, so it accepts the hit in whichever of them lists the curve.
+// AN APPROXIMATION on a plane: every cell that holds the point is tried, also one the ray's walk does not pass (a ray that lies IN the
+// plane, touches only an edge of the cell, or ends at tmax on the plane); a curve listed in such a cell alone would be hit here and
+// missed by the reference.  Off the planes (one cell holds the point) the rule is the reference's.
+// lo[a]: first such cell of axis a, cnt[a]: how many (1, or 2 on a plane); false: none.
+struct HitCells { int lo[3], cnt[3]; };
+__device__ __forceinline__ bool cells_of_hit(const DPrimSet *P, const double hp[3], HitCells *hc)
 {
-  double cmin[3], cmax[3];
-  const double hp[3] = {hitp.x, hitp.y, hitp.z};
   for (int a = 0; a < 3; a++) {
     int c = (int) floor((hp[a] - P->bounds[a]) / P->grid_cell[a]);
     c = c < 0 ? 0 : (c > P->grid_n[a] - 1 ? P->grid_n[a] - 1 : c);
-    cmin[a] = P->bounds[a] + (double) c * P->grid_cell[a];
-    cmax[a] = cmin[a] + P->grid_cell[a];
-    if (hp[a] < cmin[a] || cmax[a] < hp[a]) return false;
+    int lo = c + 1, cnt = 0;
+    for (int k = c - 1; k <= c + 1; k++) {
+      if (k < 0 || k > P->grid_n[a] - 1) continue;
+      const double kmin = P->bounds[a] + (double) k * P->grid_cell[a];
+      if (hp[a] < kmin || kmin + P->grid_cell[a] < hp[a]) continue;
+      if (k < lo) lo = k;
+      cnt++;
+    }
+    if (cnt == 0) return false;
+    hc->lo[a] = lo; hc->cnt[a] = cnt;
   }
+  return true;
+}
+
+__device__ bool curve_listed_in_cell_moving(const FJ_GLOBAL double *cpw, const FJ_GLOBAL double *velw, const double cmin[3], const double cmax[3])
+{
   const V3 r0 = ld3(cpw), r1 = ld3(cpw + 3), r2 = ld3(cpw + 6), r3 = ld3(cpw + 9);
   const V3 w0 = ld3(velw), w1 = ld3(velw + 3), w2 = ld3(velw + 6), w3 = ld3(velw + 9);
   const uint32_t depth = 5, nleaf = 32;
@@ -335,20 +353,8 @@ __device__ bool curve_listed_in_cell_of_moving(const DPrimSet *P, const FJ_GLOBA
   return false;
 }
 
-__device__ bool curve_listed_in_cell_of(const DPrimSet *P, const FJ_GLOBAL double *cpw, V3 hitp)
+__device__ bool curve_listed_in_cell(const FJ_GLOBAL double *cpw, const double cmin[3], const double cmax[3])
 {
-  int ci[3];
-  double cmin[3], cmax[3];
-  const double hp[3] = {hitp.x, hitp.y, hitp.z};
-  for (int a = 0; a < 3; a++) {
-    int c = (int) floor((hp[a] - P->bounds[a]) / P->grid_cell[a]);
-    c = c < 0 ? 0 : (c > P->grid_n[a] - 1 ? P->grid_n[a] - 1 : c);
-    ci[a] = c;
-    cmin[a] = P->bounds[a] + (double) c * P->grid_cell[a];       // get_grid_cell, :334-343
-    cmax[a] = cmin[a] + P->grid_cell[a];
-    if (hp[a] < cmin[a] || cmax[a] < hp[a]) return false;        // Box::ContainsPoint (inclusive)
-  }
-  (void) ci;
   // box_bezier3_intersect_recursive(cell, bezier, 5) with zero velocity
   const V3 r0 = ld3(cpw), r1 = ld3(cpw + 3), r2 = ld3(cpw + 6), r3 = ld3(cpw + 9);
   const uint32_t depth = 5, nleaf = 32;
@@ -386,6 +392,51 @@ __device__ bool curve_listed_in_cell_of(const DPrimSet *P, const FJ_GLOBAL doubl
     if (!pruned) j++;
   }
   return false;
+}
+
+// the hit point's cell -> is the curve listed in it.  Nearly every hit lies strictly inside the cell floor() names and ends in the first
+// lines; only a hit point on (or an ulp beyond) a cell plane goes on to the neighbours, out of line.
+template <bool kMoving>
+__device__ __noinline__ bool curve_listed_near_planes(const DPrimSet *P, const FJ_GLOBAL double *cpw, const FJ_GLOBAL double *velw, const double hp[3])
+{
+  HitCells hc;
+  if (!cells_of_hit(P, hp, &hc)) return false;
+  for (int z = hc.lo[2]; z < hc.lo[2] + hc.cnt[2]; z++)
+    for (int y = hc.lo[1]; y < hc.lo[1] + hc.cnt[1]; y++)
+      for (int x = hc.lo[0]; x < hc.lo[0] + hc.cnt[0]; x++) {
+        const int ci[3] = {x, y, z};
+        double cmin[3], cmax[3];
+        for (int a = 0; a < 3; a++) { cmin[a] = P->bounds[a] + (double) ci[a] * P->grid_cell[a]; cmax[a] = cmin[a] + P->grid_cell[a]; }
+        if (kMoving ? curve_listed_in_cell_moving(cpw, velw, cmin, cmax) : curve_listed_in_cell(cpw, cmin, cmax)) return true;
+      }
+  return false;
+}
+
+template <bool kMoving>
+__device__ __forceinline__ bool curve_listed_in_cell_of_any(const DPrimSet *P, const FJ_GLOBAL double *cpw, const FJ_GLOBAL double *velw, V3 hitp)
+{
+  double cmin[3], cmax[3];
+  const double hp[3] = {hitp.x, hitp.y, hitp.z};
+  bool on_plane = false;
+  for (int a = 0; a < 3; a++) {
+    int c = (int) floor((hp[a] - P->bounds[a]) / P->grid_cell[a]);
+    c = c < 0 ? 0 : (c > P->grid_n[a] - 1 ? P->grid_n[a] - 1 : c);
+    cmin[a] = P->bounds[a] + (double) c * P->grid_cell[a];       // get_grid_cell, :334-343
+    cmax[a] = cmin[a] + P->grid_cell[a];
+    if (hp[a] <= cmin[a] || cmax[a] <= hp[a]) on_plane = true;   // (strictly inside otherwise: Box::ContainsPoint holds)
+  }
+  if (!on_plane) return kMoving ? curve_listed_in_cell_moving(cpw, velw, cmin, cmax) : curve_listed_in_cell(cpw, cmin, cmax);
+  return curve_listed_near_planes<kMoving>(P, cpw, velw, hp);
+}
+
+__device__ bool curve_listed_in_cell_of(const DPrimSet *P, const FJ_GLOBAL double *cpw, V3 hitp)
+{
+  return curve_listed_in_cell_of_any<false>(P, cpw, nullptr, hitp);
+}
+
+__device__ bool curve_listed_in_cell_of_moving(const DPrimSet *P, const FJ_GLOBAL double *cpw, const FJ_GLOBAL double *velw, V3 hitp)
+{
+  return curve_listed_in_cell_of_any<true>(P, cpw, velw, hitp);
 }
 
 #endif

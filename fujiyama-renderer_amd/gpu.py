@@ -360,6 +360,30 @@ def host_light_hulls(scene_desc_ptr, group):
     return rec, Pl, M
 
 
+def host_curve_blas(scene_desc_ptr, curve_set):
+    """the BLAS over a curve set as scene creation builds it on the host (include/fjgpu.h: fjgpu_host_curve_blas; reads
+    FJGPU_CURVE_SEGDEPTH when called) -> dict(curve [n] int32, A [n, 3], B [n, 3], reach [n] (f32), depth [n] int32, box [n, 6] f32
+    (min xyz, max xyz), grid_n [3], grid_cell [3], bounds [6]), n = BLAS slots; no device needed"""
+    L = lib()
+    L.fjgpu_host_curve_blas.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+    L.fjgpu_host_curve_blas.restype = C.c_int
+    n = L.fjgpu_host_curve_blas(scene_desc_ptr, curve_set, None, None, None, None, 0, None, None, None)
+    if n < 0:
+        _check(n)
+    curve = np.zeros(n, dtype=np.int32)
+    cap = np.zeros((n, 7), dtype=np.float32)
+    depth = np.zeros(n, dtype=np.int32)
+    box = np.zeros((n, 6), dtype=np.float32)
+    grid_n = np.zeros(3, dtype=np.int32)
+    grid_cell = np.zeros(3, dtype=np.float64)
+    bounds = np.zeros(6, dtype=np.float64)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(min(0, L.fjgpu_host_curve_blas(scene_desc_ptr, curve_set, p(curve), p(cap), p(depth), p(box), n, p(grid_n), p(grid_cell), p(bounds))))
+    return dict(curve=curve, A=cap[:, 0:3].copy(), B=cap[:, 3:6].copy(), reach=cap[:, 6].copy(), depth=depth, box=box, grid_n=grid_n,
+                grid_cell=grid_cell, bounds=bounds)
+
+
 # the denoiser's defaults: of the grid in profiles/denoise_pass.txt (the 64 x 48 Cornell box at 2 x 2 spp against a 12 x 12 spp frame, CPU
 # oracle and numpy model) the setting with the smallest mean squared error among those that stop at instance ids
 DENOISE_ITERATIONS = 5

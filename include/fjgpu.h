@@ -486,6 +486,16 @@ int fjgpu_host_instance_level(const fj_scene_desc *desc, int group, int32_t *out
  * a negative error. */
 int fjgpu_host_light_hulls(const fj_scene_desc *desc, int group, void *out_records, double *out_Pl, int cap, double *out_M);
 
+/* Inspection, no device needed: the BLAS over curve set `curve_set` as scene creation builds it on the host (it reads
+ * FJGPU_CURVE_SEGDEPTH like scene creation does), a read-only view.  Per BLAS slot s (one piece of one curve): out_curve[s] = the
+ * curve's index in the set, out_capsule[7 s ..] = chord A xyz, chord B xyz, reach (f32, as uploaded; reach = inf with vertex
+ * velocities), out_depth[s] = the cached split depth of the curve, out_box[6 s ..] = min xyz, max xyz of the leaf box the tree holds
+ * for the slot (f32; a set of ONE slot has no node: the set's padded bounds).  out_grid_n[3], out_grid_cell[3], out_bounds[6]: the
+ * reference grid over the set that the cell-listing rule uses and the set's padded bounds.  Writes at most `cap` slots (any out
+ * pointer may be NULL); returns the slot count, or a negative error. */
+int fjgpu_host_curve_blas(const fj_scene_desc *desc, int curve_set, int32_t *out_curve, float *out_capsule, int32_t *out_depth,
+                          float *out_box, int cap, int32_t *out_grid_n, double *out_grid_cell, double *out_bounds);
+
 /* Facts about the built device scene (for measurement: record sizes of the actual layout).
  * "node_record_bytes" (128; "anyhit_node_record_bytes" 64: the lean any-hit walk reads the quantised
  * twin of a node), "tri_record_bytes" (36 when every mesh is stored as exact f32

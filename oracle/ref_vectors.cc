@@ -11,8 +11,12 @@
 // usage: ref_vectors out.bin [mesh.bin rays.bin]
 //   mesh.bin: int32 n_points, n_faces; f64 P[n_points*3]; int32 idx[n_faces*3]
 //   rays.bin: int32 n; f64 rays[n*8] (orig, dir, tmin, tmax)
+// usage: ref_vectors --curves out.bin name curves.bin rays.bin [name curves.bin rays.bin ...]
+//   (tests/golden/ref_curve_vectors.bin: the reference's own Curve under its GridAccelerator, one set of records per name)
+//   curves.bin: int32 n_points, n_curves; f64 P[n_points*3]; f64 width[n_points]; int32 idx[n_curves]
 #include "fj_box.h"
 #include "fj_camera.h"
+#include "fj_curve.h"
 #include "fj_filter.h"
 #include "fj_fixed_grid_sampler.h"
 #include "fj_grid_accelerator.h"
@@ -356,8 +360,79 @@ static int gen_mesh_trace(const char *mesh_path, const char *rays_path)
   return 0;
 }
 
+// Curve::split_depth_ is private and has no getter: a pointer to it, handed out by an explicit instantiation (which may name
+// private members)
+struct SplitDepthTag { typedef std::vector<int> Curve::*type; friend type get(SplitDepthTag); };
+template <typename Tag, typename Tag::type M> struct Expose { friend typename Tag::type get(Tag) { return M; } };
+template struct Expose<SplitDepthTag, &Curve::split_depth_>;
+
+static int gen_curve_trace(const std::string &name, const char *curves_path, const char *rays_path)
+{
+  FILE *fc = fopen(curves_path, "rb"), *fr = fopen(rays_path, "rb");
+  if (!fc || !fr) { fprintf(stderr, "ref_vectors: cannot open curves / rays file\n"); return -1; }
+  int32_t np = 0, nc = 0, nr = 0;
+  if (fread(&np, 4, 1, fc) != 1 || fread(&nc, 4, 1, fc) != 1) return -1;
+  std::vector<double> P((size_t) np * 3), width(np);
+  std::vector<int32_t> idx(nc);
+  if (fread(P.data(), 8, P.size(), fc) != P.size() || fread(width.data(), 8, width.size(), fc) != width.size() ||
+      fread(idx.data(), 4, idx.size(), fc) != idx.size()) return -1;
+  if (fread(&nr, 4, 1, fr) != 1) return -1;
+  std::vector<double> rays((size_t) nr * 8);
+  if (fread(rays.data(), 8, rays.size(), fr) != rays.size()) return -1;
+  fclose(fc); fclose(fr);
+
+  Curve curve;
+  curve.SetVertexCount(np);
+  curve.SetCurveCount(nc);
+  curve.AddVertexPosition();
+  curve.AddVertexWidth();
+  curve.AddVertexColor();
+  curve.AddCurveIndices();
+  for (int i = 0; i < np; i++) {
+    curve.SetVertexPosition(i, Vector(P[3 * i], P[3 * i + 1], P[3 * i + 2]));
+    curve.SetVertexWidth(i, width[i]);
+    curve.SetVertexColor(i, Color(1, 1, 1));
+  }
+  for (int i = 0; i < nc; i++) curve.SetCurveIndices(i, idx[i]);
+  curve.ComputeBounds();
+  GridAccelerator acc;
+  acc.SetPrimitiveSet(&curve);
+  acc.ComputeBounds();
+  acc.Build();
+
+  std::vector<double> t(nr);
+  std::vector<int32_t> hit(nr);
+  for (int i = 0; i < nr; i++) {
+    const double *r = &rays[(size_t) i * 8];
+    Ray ray;
+    ray.orig = Vector(r[0], r[1], r[2]);
+    ray.dir = Vector(r[3], r[4], r[5]);
+    ray.tmin = r[6]; ray.tmax = r[7];
+    Intersection is;
+    hit[i] = acc.Intersect(ray, 0, &is);
+    t[i] = hit[i] ? is.t_hit : 1.7976931348623157e308;
+  }
+  const std::vector<int> &sd = curve.*get(SplitDepthTag());
+  std::vector<int32_t> depth(sd.begin(), sd.end());
+  const Box &b = curve.GetBounds();
+  put_d(name + "_t", {(uint32_t) nr}, t);
+  put_i(name + "_hit", {(uint32_t) nr}, hit);
+  put_i(name + "_depth", {(uint32_t) nc}, depth);
+  put_d(name + "_bounds", {6}, {b.min.x, b.min.y, b.min.z, b.max.x, b.max.y, b.max.z});
+  return 0;
+}
+
 int main(int argc, const char **argv)
 {
+  if (argc >= 6 && std::string(argv[1]) == "--curves" && (argc - 3) % 3 == 0) {
+    g_out = fopen(argv[2], "wb");
+    if (!g_out) return 2;
+    fwrite("FJGV", 1, 4, g_out);
+    int rc = 0;
+    for (int k = 3; k + 2 < argc && !rc; k += 3) rc = gen_curve_trace(argv[k], argv[k + 1], argv[k + 2]);
+    fclose(g_out);
+    return rc ? 1 : 0;
+  }
   if (argc != 2 && argc != 4) { fprintf(stderr, "usage: ref_vectors out.bin [mesh.bin rays.bin]\n"); return 2; }
   g_out = fopen(argv[1], "wb");
   if (!g_out) return 2;

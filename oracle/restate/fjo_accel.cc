@@ -186,6 +186,8 @@ static bool primset_accel_intersect(const PrimSet &ps, const Ray &ray, double ti
   return grid_intersect(ps, ray, time, isect);
 }
 
+bool PrimSetIntersect(const PrimSet &ps, const Ray &ray, double time, Isect *isect) { return primset_accel_intersect(ps, ray, time, isect); }
+
 // ------------------------------------------------------------------ transforms
 static void lerp_channel(const fj_xform_sample *s, int n, double time, double out[3])  // src/fj_property.cc:317-345
 {

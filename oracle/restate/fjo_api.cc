@@ -73,6 +73,62 @@ int fjo_scene_grid_info(void *h, int mesh, int32_t *ncells, int64_t *entries)
   return 0;
 }
 
+// Curve::ray_intersect of listed (ray, curve) pairs of curve set `set`, WITHOUT the grid and without the ray's [tmin, tmax]:
+// rays [n][8] (object space; entries 6 and 7 are not read), curve_ids[n], times[n] (NULL: 0) -> out_hit[n], out_t[n], out_v[n]
+int fjo_curve_ray(void *h, int set, int n, const double *rays, const int32_t *curve_ids, const double *times,
+    int32_t *out_hit, double *out_t, double *out_v)
+{
+  const Scene *sc = static_cast<Scene *>(h);
+  if (set < 0 || set >= (int) sc->curves.size()) return -1;
+  const PrimSet &ps = sc->curves[set];
+  for (int i = 0; i < n; i++) {
+    const double *r = rays + 8 * i;
+    if (curve_ids[i] < 0 || curve_ids[i] >= ps.curve->n_curves) return -1;
+    Ray ray{V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), r[6], r[7]};
+    Isect is;
+    double v = 0;
+    const bool hit = CurveRayIntersect(ps, curve_ids[i], ray, times ? times[i] : 0., &is, &v);
+    out_hit[i] = hit;
+    out_t[i] = hit ? is.t_hit : REAL_MAX;
+    out_v[i] = hit ? v : 0;
+  }
+  return 0;
+}
+
+// closest hit of n object-space rays against curve set `set` ALONE, through its grid (Accelerator::Intersect): what the reference's
+// GridAccelerator over one Curve answers.  out_hit[n], out_t[n] (REAL_MAX on miss)
+int fjo_curve_set_trace(void *h, int set, int n, const double *rays, double time, int32_t *out_hit, double *out_t)
+{
+  const Scene *sc = static_cast<Scene *>(h);
+  if (set < 0 || set >= (int) sc->curves.size()) return -1;
+  for (int i = 0; i < n; i++) {
+    const double *r = rays + 8 * i;
+    Ray ray{V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), r[6], r[7]};
+    Isect is;
+    const bool hit = PrimSetIntersect(sc->curves[set], ray, time, &is);
+    out_hit[i] = hit;
+    out_t[i] = hit ? is.t_hit : REAL_MAX;
+  }
+  return 0;
+}
+
+// curve set `set`: grid cells per axis, cell sizes, the grid's (padded) bounds [6] and the cached split depth of every curve
+// (out_depth: NULL or [n_curves]); returns the number of curves
+int fjo_scene_curve_info(void *h, int set, int32_t *ncells, double *cellsize, double *bounds, int32_t *out_depth)
+{
+  const Scene *sc = static_cast<Scene *>(h);
+  if (set < 0 || set >= (int) sc->curves.size()) return -1;
+  const PrimSet &ps = sc->curves[set];
+  for (int i = 0; i < 3; i++) {
+    ncells[i] = ps.grid.ncells[i];
+    cellsize[i] = ps.grid.cellsize[i];
+    bounds[i] = ps.grid.bounds.min[i];
+    bounds[3 + i] = ps.grid.bounds.max[i];
+  }
+  if (out_depth) for (size_t i = 0; i < ps.curve_split_depth.size(); i++) out_depth[i] = ps.curve_split_depth[i];
+  return (int) ps.curve_split_depth.size();
+}
+
 // instance world bounds (merge_sampled_bounds) -> out[6]
 int fjo_scene_instance_bounds(void *h, int inst, double *out)
 {

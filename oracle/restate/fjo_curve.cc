@@ -203,7 +203,7 @@ void CurveCacheSplitDepth(PrimSet *ps)                            // :168-185
 }
 
 // Curve::ray_intersect, :187-232
-bool CurveRayIntersect(const PrimSet &ps, int prim_id, const Ray &ray, double time, Isect *isect)
+bool CurveRayIntersect(const PrimSet &ps, int prim_id, const Ray &ray, double time, Isect *isect, double *v_hit_out)
 {
   const fj_curve_desc &c = *ps.curve;
   const double ray_scale = Length(ray.dir);
@@ -218,6 +218,7 @@ bool CurveRayIntersect(const PrimSet &ps, int prim_id, const Ray &ray, double ti
   for (int i = 0; i < 4; i++) b.cp[i] = MatTransformPoint(w2r, b.cp[i]);
   double ttmp = REAL_MAX, v_hit = REAL_MAX;
   if (!converge_bezier3(b, 0, 1, depth, &v_hit, &ttmp)) return false;
+  if (v_hit_out) *v_hit_out = v_hit;
   isect->t_hit = ttmp / ray_scale;
   isect->P = ray.orig + isect->t_hit * ray.dir;
   Bez orig;

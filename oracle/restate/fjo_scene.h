@@ -83,6 +83,8 @@ struct Scene {
 void BuildScene(const fj_scene_desc *d, Scene *scene);
 bool GroupIntersect(const Scene &sc, int group, const Ray &ray, double time, Isect *isect);
 void LerpXfm(const fj_xform_desc &x, double time, Xfm *out);
+// Accelerator::Intersect of ONE primitive set in its object space (what an instance calls after transforming the ray)
+bool PrimSetIntersect(const PrimSet &ps, const Ray &ray, double time, Isect *isect);
 
 // primitives (fjo_prims.cc)
 bool TriRayIntersect(const V3 &v0, const V3 &v1, const V3 &v2, const V3 &orig, const V3 &dir,
@@ -90,7 +92,8 @@ bool TriRayIntersect(const V3 &v0, const V3 &v1, const V3 &v2, const V3 &orig, c
 bool MeshRayIntersect(const fj_mesh_desc &m, int prim_id, const Ray &ray, double time, Isect *isect);
 void MeshPrimBounds(const fj_mesh_desc &m, int prim_id, Box *b);
 bool MeshBoxIntersect(const fj_mesh_desc &m, int prim_id, const Box &box);
-bool CurveRayIntersect(const PrimSet &ps, int prim_id, const Ray &ray, double time, Isect *isect);
+// v_hit_out (optional): the curve parameter of the hit, as converge_bezier3 reports it
+bool CurveRayIntersect(const PrimSet &ps, int prim_id, const Ray &ray, double time, Isect *isect, double *v_hit_out = nullptr);
 void CurvePrimBounds(const fj_curve_desc &c, int prim_id, Box *b);
 bool CurveBoxIntersect(const fj_curve_desc &c, int prim_id, const Box &box);
 void CurveCacheSplitDepth(PrimSet *ps);

@@ -79,6 +79,50 @@ def mesh_trace_inputs(asset_dir, tmp):
     return rays
 
 
+# curve sets of tests/pathological_curves.py traced by the reference's own Curve under its GridAccelerator (ref_vectors --curves)
+CURVE_GOLDEN = ("straight_even", "zero_width", "needle", "point", "closed_loop", "hairpin", "duplicates", "chained", "flat_set",
+                "on_cell_faces", "single", "far_offset", "small_scale")
+
+
+def pack_curve_input(fam, rays):
+    """one flat f64 array: n_points, n_curves, n_rays, P, width, indices, rays (tests/golden/ref_curve_in_<family>.npy)"""
+    return np.concatenate([[len(fam["P"]), len(fam["indices"]), len(rays)], fam["P"].reshape(-1), fam["width"],
+                           fam["indices"].astype(np.float64), rays.reshape(-1)]).astype(np.float64)
+
+
+def curve_vectors(tmp, env):
+    """ref_curve_vectors.bin and its inputs: per family the object-space rays of pathological_curves.base_rays and, around the hits
+    of a first pass of the REFERENCE, the tmin / tmax brackets"""
+    import pathological_curves as pc
+    exe = os.path.join(REF, "ref_vectors")
+    args = []
+    for name in CURVE_GOLDEN:
+        fam = pc.family(name)
+        cpath = os.path.join(tmp, "curves_%s.bin" % name)
+        with open(cpath, "wb") as f:
+            f.write(struct.pack("<ii", len(fam["P"]), len(fam["indices"])))
+            np.ascontiguousarray(fam["P"], np.float64).tofile(f)
+            np.ascontiguousarray(fam["width"], np.float64).tofile(f)
+            np.ascontiguousarray(fam["indices"], np.int32).tofile(f)
+
+        def write_rays(rays, tag):
+            rpath = os.path.join(tmp, "curve_rays_%s_%s.bin" % (name, tag))
+            with open(rpath, "wb") as f:
+                f.write(struct.pack("<i", len(rays)))
+                np.ascontiguousarray(rays, np.float64).tofile(f)
+            return rpath
+        base, _ = pc.base_rays(fam, n_aimed=700)
+        first = os.path.join(tmp, "curve_first_%s.bin" % name)
+        subprocess.run([exe, "--curves", first, name, cpath, write_rays(base, "first")], check=True, env=env)
+        v = golden_io.read_vectors(first)
+        rays = np.concatenate([base, pc.bracket_rays(base, v[name + "_t"], v[name + "_hit"] != 0, n=60)], axis=0)
+        np.save(os.path.join(HERE, "ref_curve_in_%s.npy" % name), pack_curve_input(fam, rays))
+        args += [name, cpath, write_rays(rays, "all")]
+    out = os.path.join(HERE, "ref_curve_vectors.bin")
+    subprocess.run([exe, "--curves", out] + args, check=True, env=env)
+    print("wrote", out, os.path.getsize(out))
+
+
 def main():
     if not os.path.exists(os.path.join(REF, "ref_render")):
         raise SystemExit("oracle/_ref is not built: make -C oracle ref (needs /root/reference)")
@@ -86,6 +130,10 @@ def main():
     tmp = os.path.join(asset_dir, "golden_tmp")
     os.makedirs(tmp, exist_ok=True)
     env = dict(os.environ, LD_LIBRARY_PATH=REF)
+
+    curve_vectors(tmp, env)
+    if sys.argv[1:] == ["curves"]:          # only the curve vectors (the other fixtures stay as they are)
+        return
 
     rays = mesh_trace_inputs(asset_dir, tmp)
     out = os.path.join(HERE, "ref_vectors.bin")

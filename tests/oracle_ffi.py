@@ -35,6 +35,9 @@ def lib():
         L.fjo_scene_render_serial.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_void_p, C.c_int, C.c_void_p,
                                               C.POINTER(ffi.RayCounts)]
         L.fjo_scene_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fjo_curve_ray.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fjo_curve_set_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        L.fjo_scene_curve_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -89,3 +92,47 @@ class OracleScene(object):
         if e:
             raise RuntimeError("oracle trace failed: %d" % e)
         return t, ids, attr
+
+    def curve_ray(self, curve_set, rays, curve_ids, times=None):
+        """Curve::ray_intersect of (rays[i], curve curve_ids[i], times[i]) pairs of one curve set, without the grid and without
+        the ray's [tmin, tmax] (rays [n, 8] in the set's object space) -> hit [n] bool, t [n], v_hit [n]"""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        ids = np.ascontiguousarray(curve_ids, dtype=np.int32)
+        n = rays.shape[0]
+        assert ids.shape == (n,)
+        tm = None if times is None else np.ascontiguousarray(times, dtype=np.float64)
+        hit = np.empty(n, dtype=np.int32)
+        t = np.empty(n)
+        v = np.empty(n)
+        e = lib().fjo_curve_ray(self._h, curve_set, n, rays.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
+                                None if tm is None else tm.ctypes.data_as(C.c_void_p), hit.ctypes.data_as(C.c_void_p),
+                                t.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p))
+        if e:
+            raise RuntimeError("oracle curve_ray failed: %d" % e)
+        return hit != 0, t, v
+
+    def curve_set_trace(self, curve_set, rays, time=0.0):
+        """closest hits of object-space rays [n, 8] against ONE curve set through its grid, no instance level -> hit [n] bool, t [n]"""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        n = rays.shape[0]
+        hit = np.empty(n, dtype=np.int32)
+        t = np.empty(n)
+        e = lib().fjo_curve_set_trace(self._h, curve_set, n, rays.ctypes.data_as(C.c_void_p), C.c_double(time),
+                                      hit.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p))
+        if e:
+            raise RuntimeError("oracle curve_set_trace failed: %d" % e)
+        return hit != 0, t
+
+    def curve_info(self, curve_set):
+        """the reference grid over a curve set and its cached split depths -> dict(grid_n [3], grid_cell [3], bounds [6], depth [n_curves])"""
+        ncells = np.zeros(3, dtype=np.int32)
+        cell = np.zeros(3)
+        bounds = np.zeros(6)
+        n = lib().fjo_scene_curve_info(self._h, curve_set, ncells.ctypes.data_as(C.c_void_p), cell.ctypes.data_as(C.c_void_p),
+                                       bounds.ctypes.data_as(C.c_void_p), None)
+        if n < 0:
+            raise RuntimeError("oracle curve_info failed: %d" % n)
+        depth = np.zeros(n, dtype=np.int32)
+        lib().fjo_scene_curve_info(self._h, curve_set, ncells.ctypes.data_as(C.c_void_p), cell.ctypes.data_as(C.c_void_p),
+                                   bounds.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p))
+        return dict(grid_n=ncells, grid_cell=cell, bounds=bounds, depth=depth)

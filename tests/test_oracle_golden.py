@@ -8,6 +8,7 @@ product's HOST-side math (matrices, RNG tables, tiler, sampler margin) through
 the diagnostic exports of lib/libfjgpu.so -- no GPU needed.
 """
 import ctypes as C
+import glob
 import os
 
 import numpy as np
@@ -390,3 +391,65 @@ def test_reference_scene_text_through_the_parser_matches_the_reference_render(sc
     assert host.lib().fj_write_fb_file(ours.encode(), w, h, c, ref.ctypes.data_as(C.c_void_p)) == 0
     assert reference_records.sha256(ours) == ref_fb_sha256
     host.close_scene()
+
+
+# ---- curve sets: the reference's own Curve under its GridAccelerator (tests/golden/ref_curve_vectors.bin, ref_vectors --curves)
+CURVE_GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CURVE_GOLDEN_NAMES = sorted(os.path.basename(p)[len("ref_curve_in_"):-len(".npy")]
+                            for p in glob.glob(os.path.join(CURVE_GOLDEN_DIR, "ref_curve_in_*.npy")))
+
+
+def _unpack_curve_input(a):
+    n_points, n_curves, n_rays = (int(x) for x in a[:3])
+    o = 3
+    P = a[o:o + 3 * n_points].reshape(n_points, 3); o += 3 * n_points
+    width = a[o:o + n_points]; o += n_points
+    indices = a[o:o + n_curves].astype(np.int32); o += n_curves
+    rays = a[o:o + 8 * n_rays].reshape(n_rays, 8); o += 8 * n_rays
+    assert o == len(a)
+    return P, width, indices, rays
+
+
+@pytest.fixture(scope="module")
+def curve_vec(golden_dir):
+    return golden_io.read_vectors(os.path.join(golden_dir, "ref_curve_vectors.bin"))
+
+
+def test_curve_golden_covers_the_degenerate_families():
+    names = CURVE_GOLDEN_NAMES
+    assert len(names) >= 10 and {"straight_even", "zero_width", "point", "hairpin", "on_cell_faces", "far_offset", "small_scale"} <= set(names)
+
+
+@pytest.mark.parametrize("name", CURVE_GOLDEN_NAMES)
+def test_curve_grid_trace_and_split_depths_match_the_reference(name, curve_vec, golden_dir, asset_dir, monkeypatch):
+    """the oracle's grid over ONE curve set against the reference's: hit flags equal, t bit for bit (NaN equals NaN), the cached
+    split depths (the (int) of +-inf of straight and zero-width curves included) and the set's bounds; the host builder's depths
+    (fjgpu_host_curve_blas) equal the reference's too.  Rays with a NaN frame (direction exactly +-y) are in every set."""
+    import pathological_curves as pc
+    P, width, indices, rays = _unpack_curve_input(np.load(os.path.join(golden_dir, "ref_curve_in_%s.npy" % name)))
+    fam = pc.family(name)           # the committed inputs are the generator's
+    assert np.array_equal(P, fam["P"]) and np.array_equal(width, fam["width"]) and np.array_equal(indices, fam["indices"])
+    cs = pc.CurveScene(asset_dir, dict(fam, P=P, width=width, indices=indices))
+    osc = oracle_ffi.OracleScene(cs.sp)
+    try:
+        hit, t = osc.curve_set_trace(0, rays)
+        info = osc.curve_info(0)
+    finally:
+        osc.close()
+    ref_hit, ref_t = curve_vec[name + "_hit"] != 0, curve_vec[name + "_t"]
+    nan = pc.nan_frame(rays)
+    print("%-14s rays %d  reference hits %d  NaN-frame rays %d (reference hits among them %d, NaN t %d)" % (
+        name, len(rays), int(ref_hit.sum()), int(nan.sum()), int(ref_hit[nan].sum()), int(np.isnan(ref_t).sum())))
+    assert len(rays) == len(ref_t) and nan.sum() >= 150
+    assert np.array_equal(hit, ref_hit)
+    assert pc.same_t(t, ref_t)
+    assert np.array_equal(info["depth"], curve_vec[name + "_depth"])
+    assert np.array_equal(cs.bounds, curve_vec[name + "_bounds"])
+    if name not in pc.NO_HITS:
+        assert ref_hit.sum() >= pc.HIT_FLOOR and (~ref_hit).sum() >= pc.HIT_FLOOR
+    else:
+        assert ref_hit.sum() == 0
+    for seg_depth in (0, 4):
+        monkeypatch.setenv("FJGPU_CURVE_SEGDEPTH", str(seg_depth))
+        blas = gpu.host_curve_blas(cs.sp, 0)
+        assert np.array_equal(blas["depth"], curve_vec[name + "_depth"][blas["curve"]])
