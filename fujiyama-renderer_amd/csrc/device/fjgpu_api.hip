@@ -1,5 +1,6 @@
-// fjgpu_api.hip -- C ABI of libfjgpu.so (include/fjgpu.h): device scene
-// residency, the wavefront batch loop, and the ray-batch trace entry point.
+// fjgpu_api.hip -- C ABI of libfjgpu.so (include/fjgpu.h), the entry points that take a fjgpu_scene: device scene
+// residency, the wavefront batch loop, the ray-batch trace entry point, the AOV pass and the camera of a resident scene.
+// (the image-space passes, which take only buffers, are in fjgpu_image_api.hip)
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <map>
@@ -21,10 +22,8 @@
 #include <vector>
 
 #include "fjgpu.h"
+#include "fjgpu_api_common.h"
 #include "fjgpu_build.h"
-#include "fjgpu_denoise.h"
-#include "fjgpu_denoise_variance.h"
-#include "fjgpu_temporal.h"
 #include "fjgpu_kernels.h"
 #include "fjgpu_lbvh.h"
 #include "fjgpu_light_cone.h"
@@ -32,47 +31,21 @@
 #include "fjgpu_raysort.h"
 #include "fjgpu_tlas.h"
 
-namespace {
+// the ONE error text of the library: every translation unit sets it through fjgpu::fail (fjgpu_api_common.h)
+static thread_local std::string t_last_error;
 
-thread_local std::string t_last_error;
-
-int fail(int code, const std::string &msg)
+int fjgpu::fail(int code, const std::string &msg)
 {
   t_last_error = msg;
   return code;
 }
 
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-  return fail(FJGPU_ENODEV, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+namespace {
+
+using fjgpu::fail;
+using fjgpu::DeviceBuffers;
 
 #define FJ_LREC_BUFS 4
-
-struct DeviceBuffers {
-  std::vector<void *> ptrs;
-  size_t bytes = 0;
-  ~DeviceBuffers() { for (void *p : ptrs) (void) hipFree(p); }
-  template <class T> int upload(const T *src, size_t n, const T **out)
-  {
-    *out = nullptr;
-    if (n == 0 || src == nullptr) return 0;
-    void *d = nullptr;
-    if (hipMalloc(&d, n * sizeof(T)) != hipSuccess) return -1;
-    ptrs.push_back(d);
-    bytes += n * sizeof(T);
-    if (hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return -1;
-    *out = static_cast<const T *>(d);
-    return 0;
-  }
-  template <class T> int alloc(size_t n, T **out)
-  {
-    void *d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return -1;
-    ptrs.push_back(d);
-    bytes += std::max<size_t>(n, 1) * sizeof(T);
-    *out = static_cast<T *>(d);
-    return 0;
-  }
-};
 
 // ---- RCCL, loaded at first use (no link-time dependency: the single-device paths never need it).  The slab exchange of
 // fjgpu_render_frame_multi in RCCL's spelling -- ncclGroupStart / ncclSend / ncclRecv / ncclGroupEnd, SURVEY 8(e) -- beside the peer copy.
@@ -2562,244 +2535,6 @@ int fjgpu_render_aov_albedo(fjgpu_scene *sc, const fj_render_desc *r, const int3
   return render_aov_body("fjgpu_render_aov_albedo", sc, r, tile_ids, n_tiles, out, d_albedo, hip_stream, stats);
 }
 
-// ---- denoiser (fjgpu_denoise.hip, fjgpu_denoise_math.h).  Shaped like the AOV pass: no scene, transient buffers per call -- two RGBA frames
-// of the region for the iterations to ping-pong between and one 32-byte guide record per region pixel.  Iteration 0 reads color_in and the
-// last one writes color_out, every other end of an iteration is a scratch frame, so color_out may be color_in: with two or more iterations
-// no launch reads what it writes, and a single iteration in place filters a copy of the region.
-// (the refusals keep fjgpu_denoise's name in their messages, whichever of the two entry points was called: with albedo NULL they are the same call)
-int fjgpu_denoise_albedo(int device, const fjgpu_denoise_desc *d, const float *color_in, const float *normal, const float *position,
-    const int32_t *ids, const float *albedo, float albedo_floor, float *color_out, void *hip_stream, fjgpu_stats *stats)
-{
-  if (albedo && !(std::isfinite(albedo_floor) && albedo_floor > 0))
-    return fail(FJGPU_EINVAL, "fjgpu_denoise_albedo: albedo_floor must be finite and > 0");
-  if (!d || !color_in || !color_out) return fail(FJGPU_EINVAL, "fjgpu_denoise: null argument (desc, color_in and color_out are required)");
-  if (d->xres <= 0 || d->yres <= 0) return fail(FJGPU_EINVAL, "fjgpu_denoise: resolution must be positive");
-  if (d->region[0] < 0 || d->region[1] < 0 || d->region[2] > d->xres || d->region[3] > d->yres ||
-      d->region[0] >= d->region[2] || d->region[1] >= d->region[3])
-    return fail(FJGPU_EINVAL, "fjgpu_denoise: region must be a non-empty rectangle inside the frame");
-  if (d->iterations < 1 || d->iterations > FJ_DN_MAX_ITERATIONS) return fail(FJGPU_EINVAL, "fjgpu_denoise: iterations must be 1..8");
-  if (std::isnan(d->sigma_color) || std::isnan(d->sigma_normal) || std::isnan(d->sigma_position))
-    return fail(FJGPU_EINVAL, "fjgpu_denoise: a sigma is NaN");
-  if (((uintptr_t) color_in | (uintptr_t) color_out) & 15u) return fail(FJGPU_EINVAL, "fjgpu_denoise: color_in and color_out must be 16-byte aligned");
-  const int w = d->region[2] - d->region[0], h = d->region[3] - d->region[1];
-  if (h > 65535 * 4) return fail(FJGPU_EINVAL, "fjgpu_denoise: a region of more than 262140 rows");
-  if (fjgpu_device_count() < 1) return fail(FJGPU_ENODEV, "fjgpu_denoise: no HIP device is visible");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  const size_t npx = (size_t) w * (size_t) h;
-  const int n_it = d->iterations;
-  const int stop = (d->stop_at_ids && ids) ? 1 : 0;
-
-  DeviceBuffers W;
-  float *d_frame[2], *d_guide;
-  if (W.alloc(npx * 4, &d_frame[0]) || W.alloc(npx * 4, &d_frame[1]) || W.alloc(npx * 8, &d_guide))
-    return fail(FJGPU_ENOMEM, "fjgpu_denoise: device allocation failed");
-
-  fjgpu_stats acc;
-  std::memset(&acc, 0, sizeof(acc));
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};      // call start, guide pack done, iterations done
-  int rc = 0;
-  for (int k = 0; k < 3 && !rc; k++) if (hipEventCreate(&ev[k]) != hipSuccess) rc = -1;
-  const size_t origin = ((size_t) d->region[1] * (size_t) d->xres + (size_t) d->region[0]) * 4;
-  if (!rc) {
-    (void) hipEventRecord(ev[0], st);
-    rc = launch_dn_pack(st, normal, position, ids, d->xres, d->region[0], d->region[1], w, h, d_guide);
-    (void) hipEventRecord(ev[1], st);
-  }
-  const float *src = color_in + origin;
-  int src_stride = d->xres;
-  if (!rc && albedo) {
-    // the filter's input is colour / albedo, staged in the scratch frame iteration 0 does not write (iteration 1 is the first to)
-    rc = launch_dn_demodulate(st, src, d->xres, albedo, d->xres, d->region[0], d->region[1], albedo_floor, d_frame[1], w, w, h);
-    src = d_frame[1]; src_stride = w;
-    if (ev[1]) (void) hipEventRecord(ev[1], st);      // (gen_ms: the guide pack and this copy)
-  } else if (!rc && n_it == 1 && color_in == color_out) {
-    // in place with a single iteration: that launch would read pixels other blocks have written
-    if (hipMemcpy2DAsync(d_frame[1], (size_t) w * 16, src, (size_t) d->xres * 16, (size_t) w * 16, (size_t) h, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = -1;
-    src = d_frame[1]; src_stride = w;
-  }
-  for (int i = 0; i < n_it && !rc; i++) {
-    const bool last = i == n_it - 1;
-    float *dst = last ? color_out + origin : d_frame[i & 1];
-    const int dst_stride = last ? d->xres : w;
-    rc = launch_dn_atrous(st, src, src_stride, d_guide, dst, dst_stride, w, h, 1 << i, stop,
-                          fj_dn_constants(d->sigma_color, normal ? d->sigma_normal : 0.f, position ? d->sigma_position : 0.f, i));
-    src = dst; src_stride = dst_stride;
-  }
-  if (!rc && albedo) rc = launch_dn_remodulate(st, color_out + origin, d->xres, albedo, d->xres, d->region[0], d->region[1], albedo_floor, w, h);
-  if (ev[2]) (void) hipEventRecord(ev[2], st);
-  const hipError_t se = hipStreamSynchronize(st);      // (also before the transient buffers go away)
-  if (rc == 0 && se == hipSuccess) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) acc.gen_ms = ms;
-    if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) acc.resolve_ms = ms;
-    if (hipEventElapsedTime(&ms, ev[0], ev[2]) == hipSuccess) acc.total_ms = ms;
-    acc.batches = (uint32_t) n_it;
-  }
-  for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
-  if (rc) return fail(FJGPU_ENODEV, std::string("fjgpu_denoise: HIP failure: ") + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
-  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string("fjgpu_denoise: stream synchronize: ") + hipGetErrorString(se));
-  if (stats) *stats = acc;
-  return 0;
-}
-
-int fjgpu_denoise(int device, const fjgpu_denoise_desc *d, const float *color_in, const float *normal, const float *position,
-    const int32_t *ids, float *color_out, void *hip_stream, fjgpu_stats *stats)
-{
-  return fjgpu_denoise_albedo(device, d, color_in, normal, position, ids, nullptr, 0.f, color_out, hip_stream, stats);
-}
-
-// ---- variance-guided denoiser (fjgpu_denoise_variance.hip, fjgpu_denoise_var_math.h).  fjgpu_denoise's shape and scratch, plus two f32
-// planes of the region: the estimate (or nothing, where the caller brings a variance) lands in one, the iterations ping-pong between them.
-namespace {
-
-// the refusals both entry points share, each naming `fn`; 0 or the error
-int dnv_check(const char *fn, const fjgpu_denoise_desc *d, const float *color, bool with_iterations)
-{
-  const std::string f(fn);
-  if (d->xres <= 0 || d->yres <= 0) return fail(FJGPU_EINVAL, f + ": resolution must be positive");
-  if (d->region[0] < 0 || d->region[1] < 0 || d->region[2] > d->xres || d->region[3] > d->yres ||
-      d->region[0] >= d->region[2] || d->region[1] >= d->region[3])
-    return fail(FJGPU_EINVAL, f + ": region must be a non-empty rectangle inside the frame");
-  if (with_iterations && (d->iterations < 1 || d->iterations > FJ_DN_MAX_ITERATIONS)) return fail(FJGPU_EINVAL, f + ": iterations must be 1..8");
-  if (std::isnan(d->sigma_color) || std::isnan(d->sigma_normal) || std::isnan(d->sigma_position)) return fail(FJGPU_EINVAL, f + ": a sigma is NaN");
-  if ((uintptr_t) color & 15u) return fail(FJGPU_EINVAL, f + ": colour buffers must be 16-byte aligned");
-  if (d->region[3] - d->region[1] > 65535 * 4) return fail(FJGPU_EINVAL, f + ": a region of more than 262140 rows");
-  return 0;
-}
-
-}  // namespace
-
-int fjgpu_denoise_estimate_variance(int device, const fjgpu_denoise_desc *d, const float *color, const float *normal, const float *position,
-    const int32_t *ids, float *variance_out, void *hip_stream, fjgpu_stats *stats)
-{
-  const char *fn = "fjgpu_denoise_estimate_variance";
-  if (!d || !color || !variance_out)
-    return fail(FJGPU_EINVAL, std::string(fn) + ": null argument (desc, color and variance_out are required)");
-  if (const int e = dnv_check(fn, d, color, false)) return e;
-  if ((const void *) variance_out == (const void *) color) return fail(FJGPU_EINVAL, std::string(fn) + ": variance_out must not be the colour buffer");
-  if (fjgpu_device_count() < 1) return fail(FJGPU_ENODEV, std::string(fn) + ": no HIP device is visible");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  const int w = d->region[2] - d->region[0], h = d->region[3] - d->region[1];
-  const size_t npx = (size_t) w * (size_t) h;
-  const int stop = (d->stop_at_ids && ids) ? 1 : 0;
-  DeviceBuffers W;
-  float *d_guide;
-  if (W.alloc(npx * 8, &d_guide)) return fail(FJGPU_ENOMEM, std::string(fn) + ": device allocation failed");
-  fjgpu_stats acc;
-  std::memset(&acc, 0, sizeof(acc));
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int rc = 0;
-  for (int k = 0; k < 2 && !rc; k++) if (hipEventCreate(&ev[k]) != hipSuccess) rc = -1;
-  const size_t origin = (size_t) d->region[1] * (size_t) d->xres + (size_t) d->region[0];
-  if (!rc) {
-    (void) hipEventRecord(ev[0], st);
-    rc = launch_dn_pack_var(st, color + origin * 4, d->xres, normal, position, ids, d->xres, d->region[0], d->region[1], w, h, d_guide);
-    if (!rc) rc = launch_dn_variance(st, d_guide, variance_out + origin, d->xres, w, h, stop,
-                                     fj_dn_constants(0.f, normal ? d->sigma_normal : 0.f, position ? d->sigma_position : 0.f, 0));
-    (void) hipEventRecord(ev[1], st);
-  }
-  const hipError_t se = hipStreamSynchronize(st);      // (also before the transient buffer goes away)
-  if (rc == 0 && se == hipSuccess) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) acc.gen_ms = acc.total_ms = ms;
-  }
-  for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
-  if (rc) return fail(FJGPU_ENODEV, std::string(fn) + ": HIP failure: " + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
-  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string(fn) + ": stream synchronize: " + hipGetErrorString(se));
-  if (stats) *stats = acc;
-  return 0;
-}
-
-int fjgpu_denoise_variance(int device, const fjgpu_denoise_desc *d, float sigma_luminance, const float *color_in, const float *normal,
-    const float *position, const int32_t *ids, const float *albedo, float albedo_floor, const float *variance_in, float *color_out,
-    float *variance_out, void *hip_stream, fjgpu_stats *stats)
-{
-  const char *fn = "fjgpu_denoise_variance";
-  if (albedo && !(std::isfinite(albedo_floor) && albedo_floor > 0))
-    return fail(FJGPU_EINVAL, std::string(fn) + ": albedo_floor must be finite and > 0");
-  if (!d || !color_in || !color_out)
-    return fail(FJGPU_EINVAL, std::string(fn) + ": null argument (desc, color_in and color_out are required)");
-  if (const int e = dnv_check(fn, d, (const float *) ((uintptr_t) color_in | (uintptr_t) color_out), true)) return e;
-  if (std::isnan(sigma_luminance)) return fail(FJGPU_EINVAL, std::string(fn) + ": sigma_luminance is NaN");
-  if (variance_out && ((const void *) variance_out == (const void *) variance_in || (const void *) variance_out == (const void *) color_in ||
-                       (const void *) variance_out == (const void *) color_out))
-    return fail(FJGPU_EINVAL, std::string(fn) + ": variance_out must not be variance_in or a colour buffer");
-  if (variance_in && ((const void *) variance_in == (const void *) color_out))
-    return fail(FJGPU_EINVAL, std::string(fn) + ": variance_in must not be color_out");
-  if (fjgpu_device_count() < 1) return fail(FJGPU_ENODEV, std::string(fn) + ": no HIP device is visible");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  const int w = d->region[2] - d->region[0], h = d->region[3] - d->region[1];
-  const size_t npx = (size_t) w * (size_t) h;
-  const int n_it = d->iterations;
-  const int stop = (d->stop_at_ids && ids) ? 1 : 0;
-  const DnConst k = fj_dn_constants(0.f, normal ? d->sigma_normal : 0.f, position ? d->sigma_position : 0.f, 0);
-
-  DeviceBuffers W;
-  float *d_frame[2], *d_guide, *d_var[2];
-  if (W.alloc(npx * 4, &d_frame[0]) || W.alloc(npx * 4, &d_frame[1]) || W.alloc(npx * 8, &d_guide) || W.alloc(npx, &d_var[0]) ||
-      W.alloc(npx, &d_var[1]))
-    return fail(FJGPU_ENOMEM, std::string(fn) + ": device allocation failed");
-
-  fjgpu_stats acc;
-  std::memset(&acc, 0, sizeof(acc));
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};      // call start, pack / demodulation / estimate done, iterations done
-  int rc = 0;
-  for (int e = 0; e < 3 && !rc; e++) if (hipEventCreate(&ev[e]) != hipSuccess) rc = -1;
-  const size_t origin = (size_t) d->region[1] * (size_t) d->xres + (size_t) d->region[0];
-  const float *src = color_in + origin * 4;
-  int src_stride = d->xres;
-  if (!rc) (void) hipEventRecord(ev[0], st);
-  if (!rc && albedo) {
-    // the filter's input is colour / albedo, staged in the scratch frame iteration 0 does not write (iteration 1 is the first to)
-    rc = launch_dn_demodulate(st, src, d->xres, albedo, d->xres, d->region[0], d->region[1], albedo_floor, d_frame[1], w, w, h);
-    src = d_frame[1]; src_stride = w;
-  } else if (!rc && n_it == 1 && color_in == color_out) {
-    // in place with a single iteration: that launch would read pixels other blocks have written
-    if (hipMemcpy2DAsync(d_frame[1], (size_t) w * 16, src, (size_t) d->xres * 16, (size_t) w * 16, (size_t) h, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = -1;
-    src = d_frame[1]; src_stride = w;
-  }
-  const float *vin = variance_in ? variance_in + origin : d_var[0];
-  int vin_stride = variance_in ? d->xres : w;
-  if (!rc && variance_in) {
-    rc = launch_dn_pack(st, normal, position, ids, d->xres, d->region[0], d->region[1], w, h, d_guide);
-  } else if (!rc) {
-    // the estimate is of the frame the iterations filter: the demodulated one where there is an albedo
-    rc = launch_dn_pack_var(st, src, src_stride, normal, position, ids, d->xres, d->region[0], d->region[1], w, h, d_guide);
-    if (!rc) rc = launch_dn_variance(st, d_guide, d_var[0], w, w, h, stop, k);
-  }
-  if (ev[1]) (void) hipEventRecord(ev[1], st);
-  for (int i = 0; i < n_it && !rc; i++) {
-    const bool last = i == n_it - 1;
-    float *dst = last ? color_out + origin * 4 : d_frame[i & 1];
-    const int dst_stride = last ? d->xres : w;
-    // iteration i reads d_var[i & 1] (iteration 0: that or the caller's plane) and writes the other
-    float *vout = (last && variance_out) ? variance_out + origin : d_var[(i + 1) & 1];
-    const int vout_stride = (last && variance_out) ? d->xres : w;
-    rc = launch_dn_atrous_var(st, src, src_stride, d_guide, vin, vin_stride, dst, dst_stride, vout, vout_stride, w, h, 1 << i, stop,
-                              sigma_luminance, k);
-    src = dst; src_stride = dst_stride;
-    vin = vout; vin_stride = vout_stride;
-  }
-  if (!rc && albedo) rc = launch_dn_remodulate(st, color_out + origin * 4, d->xres, albedo, d->xres, d->region[0], d->region[1], albedo_floor, w, h);
-  if (ev[2]) (void) hipEventRecord(ev[2], st);
-  const hipError_t se = hipStreamSynchronize(st);      // (also before the transient buffers go away)
-  if (rc == 0 && se == hipSuccess) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) acc.gen_ms = ms;
-    if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) acc.resolve_ms = ms;
-    if (hipEventElapsedTime(&ms, ev[0], ev[2]) == hipSuccess) acc.total_ms = ms;
-    acc.batches = (uint32_t) n_it;
-  }
-  for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
-  if (rc) return fail(FJGPU_ENODEV, std::string(fn) + ": HIP failure: " + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
-  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string(fn) + ": stream synchronize: " + hipGetErrorString(se));
-  if (stats) *stats = acc;
-  return 0;
-}
-
 int fjgpu_camera_samples(fjgpu_scene *sc, const fj_render_desc *r, int tile_id, double *rays8, int cap)
 {
   if (!sc || !r || (!rays8 && cap > 0) || cap < 0) return fail(FJGPU_EINVAL, "fjgpu_camera_samples: null argument");
@@ -2831,55 +2566,6 @@ int fjgpu_camera_samples(fjgpu_scene *sc, const fj_render_desc *r, int tile_id, 
     rays8[8 * i + 6] = S.cam_znear; rays8[8 * i + 7] = S.cam_zfar;      // the range of a camera ray (Camera::GetRay, src/fj_camera.cc:105-106)
   }
   return (int) n;
-}
-
-// fjgpu_denoise_estimate_variance of the frame divided by its albedo: the first stage of fjgpu_denoise_variance with an albedo (the same
-// launches in the same order) with the estimate as the result -- the spatial fallback of fjgpu_denoise_temporal, whose moments are those of
-// the demodulated luminance.
-int fjgpu_denoise_estimate_variance_albedo(int device, const fjgpu_denoise_desc *d, const float *color, const float *normal, const float *position,
-    const int32_t *ids, const float *albedo, float albedo_floor, float *variance_out, void *hip_stream, fjgpu_stats *stats)
-{
-  if (!albedo) return fjgpu_denoise_estimate_variance(device, d, color, normal, position, ids, variance_out, hip_stream, stats);
-  const char *fn = "fjgpu_denoise_estimate_variance_albedo";
-  if (!(std::isfinite(albedo_floor) && albedo_floor > 0)) return fail(FJGPU_EINVAL, std::string(fn) + ": albedo_floor must be finite and > 0");
-  if (!d || !color || !variance_out)
-    return fail(FJGPU_EINVAL, std::string(fn) + ": null argument (desc, color and variance_out are required)");
-  if (const int e = dnv_check(fn, d, color, false)) return e;
-  if ((const void *) variance_out == (const void *) color || (const void *) variance_out == (const void *) albedo)
-    return fail(FJGPU_EINVAL, std::string(fn) + ": variance_out must not be the colour or the albedo buffer");
-  if (fjgpu_device_count() < 1) return fail(FJGPU_ENODEV, std::string(fn) + ": no HIP device is visible");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  const int w = d->region[2] - d->region[0], h = d->region[3] - d->region[1];
-  const size_t npx = (size_t) w * (size_t) h;
-  const int stop = (d->stop_at_ids && ids) ? 1 : 0;
-  DeviceBuffers W;
-  float *d_guide, *d_dem;
-  if (W.alloc(npx * 8, &d_guide) || W.alloc(npx * 4, &d_dem)) return fail(FJGPU_ENOMEM, std::string(fn) + ": device allocation failed");
-  fjgpu_stats acc;
-  std::memset(&acc, 0, sizeof(acc));
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int rc = 0;
-  for (int k = 0; k < 2 && !rc; k++) if (hipEventCreate(&ev[k]) != hipSuccess) rc = -1;
-  const size_t origin = (size_t) d->region[1] * (size_t) d->xres + (size_t) d->region[0];
-  if (!rc) {
-    (void) hipEventRecord(ev[0], st);
-    rc = launch_dn_demodulate(st, color + origin * 4, d->xres, albedo, d->xres, d->region[0], d->region[1], albedo_floor, d_dem, w, w, h);
-    if (!rc) rc = launch_dn_pack_var(st, d_dem, w, normal, position, ids, d->xres, d->region[0], d->region[1], w, h, d_guide);
-    if (!rc) rc = launch_dn_variance(st, d_guide, variance_out + origin, d->xres, w, h, stop,
-                                     fj_dn_constants(0.f, normal ? d->sigma_normal : 0.f, position ? d->sigma_position : 0.f, 0));
-    (void) hipEventRecord(ev[1], st);
-  }
-  const hipError_t se = hipStreamSynchronize(st);      // (also before the transient buffers go away)
-  if (rc == 0 && se == hipSuccess) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) acc.gen_ms = acc.total_ms = ms;
-  }
-  for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
-  if (rc) return fail(FJGPU_ENODEV, std::string(fn) + ": HIP failure: " + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
-  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string(fn) + ": stream synchronize: " + hipGetErrorString(se));
-  if (stats) *stats = acc;
-  return 0;
 }
 
 // ---- camera of a resident scene.  Host state only: the four fields every render call copies into its launch parameters.
@@ -2927,107 +2613,6 @@ int fjgpu_scene_view(const fjgpu_scene *sc, const fj_render_desc *r, fjgpu_view 
   out->uv_size[1] = fjgpu::CameraUvSizeY(sc->cam_fov);
   out->uv_size[0] = out->uv_size[1] * aspect;
   out->xres = r->xres; out->yres = r->yres;
-  return 0;
-}
-
-// ---- temporal accumulation (fjgpu_temporal.hip, fjgpu_temporal_math.h).  One launch, no scratch: every refusal is decided before a device call.
-namespace {
-
-bool tp_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-  if (!a || !b) return false;
-  const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
-}  // namespace
-
-int fjgpu_denoise_temporal(int device, const fjgpu_temporal_desc *d, const float *color, const float *position, const float *normal,
-    const int32_t *ids, const float *albedo, const float *variance_spatial, const fjgpu_view *prev_view, const float *prev_position,
-    const float *prev_normal, const int32_t *prev_ids, const fjgpu_temporal_history *prev, const fjgpu_temporal_history *next,
-    float *variance_out, void *hip_stream, fjgpu_stats *stats)
-{
-  const std::string f("fjgpu_denoise_temporal");
-  if (!d || !color) return fail(FJGPU_EINVAL, f + ": null argument (desc and color are required)");
-  if (!position || !normal || !ids) return fail(FJGPU_EINVAL, f + ": null guide (position, normal and ids are required: without them there is nothing to reproject)");
-  if (!next || !next->color || !next->moments || !next->length) return fail(FJGPU_EINVAL, f + ": null history (next and its three buffers are required)");
-  if (prev && (!prev->color || !prev->moments || !prev->length)) return fail(FJGPU_EINVAL, f + ": null history (prev is set, so are its three buffers)");
-  if (prev && (!prev_view || !prev_position || !prev_normal || !prev_ids))
-    return fail(FJGPU_EINVAL, f + ": null previous frame (prev is set: prev_view, prev_position, prev_normal and prev_ids are required)");
-  if (d->xres <= 0 || d->yres <= 0) return fail(FJGPU_EINVAL, f + ": resolution must be positive");
-  if (d->region[0] < 0 || d->region[1] < 0 || d->region[2] > d->xres || d->region[3] > d->yres ||
-      d->region[0] >= d->region[2] || d->region[1] >= d->region[3])
-    return fail(FJGPU_EINVAL, f + ": region must be a non-empty rectangle inside the frame");
-  if (std::isnan(d->alpha_min) || std::isnan(d->max_history) || std::isnan(d->tol_position) || std::isnan(d->cos_normal) ||
-      std::isnan(d->min_history_variance) || std::isnan(d->albedo_floor))
-    return fail(FJGPU_EINVAL, f + ": a parameter is NaN");
-  if (!(d->alpha_min > 0.f && d->alpha_min <= 1.f)) return fail(FJGPU_EINVAL, f + ": alpha_min must be in (0, 1]");
-  if (!(d->max_history >= 1.f)) return fail(FJGPU_EINVAL, f + ": max_history must be >= 1");
-  if (albedo && !(std::isfinite(d->albedo_floor) && d->albedo_floor > 0)) return fail(FJGPU_EINVAL, f + ": albedo_floor must be finite and > 0");
-  if (prev && (prev_view->xres <= 0 || prev_view->yres <= 0)) return fail(FJGPU_EINVAL, f + ": prev_view's resolution must be positive");
-  if (((uintptr_t) color | (uintptr_t) next->color | (uintptr_t) (prev ? prev->color : nullptr)) & 15u)
-    return fail(FJGPU_EINVAL, f + ": colour buffers must be 16-byte aligned");
-  if (d->region[3] - d->region[1] > 65535 * 16) return fail(FJGPU_EINVAL, f + ": a region of more than 1048560 rows");
-  {
-    const size_t px = (size_t) d->xres * (size_t) d->yres * sizeof(float);
-    const struct { const void *p; size_t n; } outs[4] = {{next->color, 4 * px}, {next->moments, 2 * px}, {next->length, px}, {variance_out, px}};
-    const struct { const void *p; size_t n; } ins[12] = {{color, 4 * px}, {position, 3 * px}, {normal, 3 * px}, {ids, 4 * px}, {albedo, 3 * px},
-        {variance_spatial, px}, {prev ? prev_position : nullptr, 3 * px}, {prev ? prev_normal : nullptr, 3 * px}, {prev ? prev_ids : nullptr, 4 * px},
-        {prev ? prev->color : nullptr, 4 * px}, {prev ? prev->moments : nullptr, 2 * px}, {prev ? prev->length : nullptr, px}};
-    for (int a = 0; a < 4; a++) {
-      for (int b = 0; b < 12; b++)
-        if (tp_overlap(outs[a].p, outs[a].n, ins[b].p, ins[b].n))
-          return fail(FJGPU_EINVAL, f + ": an output buffer (next, variance_out) overlaps prev or an input");
-      for (int b = a + 1; b < 4; b++)
-        if (tp_overlap(outs[a].p, outs[a].n, outs[b].p, outs[b].n)) return fail(FJGPU_EINVAL, f + ": output buffers (next, variance_out) overlap each other");
-    }
-  }
-  if (fjgpu_device_count() < 1) return fail(FJGPU_ENODEV, f + ": no HIP device is visible");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-
-  TpParams k;
-  std::memset(&k, 0, sizeof(k));
-  if (prev) {
-    std::memcpy(k.w2c, prev_view->world_to_camera, sizeof(k.w2c));
-    k.uv_size[0] = prev_view->uv_size[0]; k.uv_size[1] = prev_view->uv_size[1];
-    k.view_xres = prev_view->xres; k.view_yres = prev_view->yres;
-  }
-  k.xres = d->xres; k.yres = d->yres;
-  k.x0 = d->region[0]; k.y0 = d->region[1]; k.x1 = d->region[2]; k.y1 = d->region[3];
-  k.alpha_min = d->alpha_min; k.max_history = d->max_history;
-  k.min_history_variance = d->min_history_variance; k.albedo_floor = d->albedo_floor;
-  fj_tp_terms(d->tol_position, d->cos_normal, &k);
-  TpBuffers B;
-  std::memset(&B, 0, sizeof(B));
-  B.color = color; B.position = position; B.normal = normal; B.ids = ids; B.albedo = albedo; B.variance_spatial = variance_spatial;
-  if (prev) {
-    B.prev_position = prev_position; B.prev_normal = prev_normal; B.prev_ids = prev_ids;
-    B.prev_color = prev->color; B.prev_moments = prev->moments; B.prev_length = prev->length;
-  }
-  B.next_color = next->color; B.next_moments = next->moments; B.next_length = next->length;
-  B.variance_out = variance_out;
-
-  fjgpu_stats acc;
-  std::memset(&acc, 0, sizeof(acc));
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int rc = 0;
-  for (int e = 0; e < 2 && !rc; e++) if (hipEventCreate(&ev[e]) != hipSuccess) rc = -1;
-  if (!rc) {
-    (void) hipEventRecord(ev[0], st);
-    rc = launch_tp_accumulate(st, k, B);
-    (void) hipEventRecord(ev[1], st);
-  }
-  const hipError_t se = hipStreamSynchronize(st);
-  if (rc == 0 && se == hipSuccess) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) acc.resolve_ms = acc.total_ms = ms;
-    acc.batches = 1;
-  }
-  for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
-  if (rc) return fail(FJGPU_ENODEV, f + ": HIP failure: " + hipGetErrorString(rc > 0 ? (hipError_t) rc : hipGetLastError()));
-  if (se != hipSuccess) return fail(FJGPU_ENODEV, f + ": stream synchronize: " + hipGetErrorString(se));
-  if (stats) *stats = acc;
   return 0;
 }
 

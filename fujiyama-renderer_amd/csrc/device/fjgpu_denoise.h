@@ -1,4 +1,4 @@
-// fjgpu_denoise.h -- launchers of the denoiser's kernels (fjgpu_denoise.hip); the C entry point fjgpu_denoise is in fjgpu_api.hip
+// fjgpu_denoise.h -- launchers of the denoiser's kernels (fjgpu_denoise.hip); the C entry point fjgpu_denoise is in fjgpu_image_api.hip
 #ifndef FJGPU_DENOISE_H
 #define FJGPU_DENOISE_H
 

@@ -1,5 +1,5 @@
 // fjgpu_denoise_variance.h -- launchers of the variance-guided denoiser's kernels (fjgpu_denoise_variance.hip); the C entry points
-// fjgpu_denoise_estimate_variance and fjgpu_denoise_variance are in fjgpu_api.hip
+// fjgpu_denoise_estimate_variance and fjgpu_denoise_variance are in fjgpu_image_api.hip
 #ifndef FJGPU_DENOISE_VARIANCE_H
 #define FJGPU_DENOISE_VARIANCE_H
 

@@ -1,5 +1,5 @@
 // fjgpu_temporal.h -- launcher of the temporal accumulation's kernel (fjgpu_temporal.hip); the C entry point fjgpu_denoise_temporal is in
-// fjgpu_api.hip
+// fjgpu_image_api.hip
 #ifndef FJGPU_TEMPORAL_H
 #define FJGPU_TEMPORAL_H
 
