@@ -29,6 +29,7 @@
 #include "fjgpu_light_cone.h"
 #include "fjgpu_light_hull.h"
 #include "fjgpu_raysort.h"
+#include "fjgpu_sample_variance.h"
 #include "fjgpu_tlas.h"
 
 // the ONE error text of the library: every translation unit sets it through fjgpu::fail (fjgpu_api_common.h)
@@ -1568,15 +1569,17 @@ int ensure_sort(fjgpu_scene *sc, size_t cap)
 
 extern "C" {
 
-static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
-    float *d_fb, void *hip_stream, fjgpu_stats *stats);
+// fjgpu_render_tiles_variance's part of a call: where the variance of the listed tiles' pixels goes and, optionally, the albedo it is taken under
+struct SampleVarianceOut { float *variance; const float *albedo; float albedo_floor; };
 
-int fjgpu_render_tiles(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
-    float *d_fb, void *hip_stream, fjgpu_stats *stats)
+static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
+    float *d_fb, void *hip_stream, fjgpu_stats *stats, const SampleVarianceOut *sv = nullptr);
+
+static int render_tiles_retrying(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
+    float *d_fb, void *hip_stream, fjgpu_stats *stats, const SampleVarianceOut *sv)
 {
-  if (!sc || !r || !d_fb) return fail(FJGPU_EINVAL, "null argument");
   sc->split_overflowed = false;
-  int e = render_tiles_once(sc, r, tile_ids, n_tiles, d_fb, hip_stream, stats);
+  int e = render_tiles_once(sc, r, tile_ids, n_tiles, d_fb, hip_stream, stats, sv);
   if (e == FJGPU_ENOMEM && sc->split_overflowed) {
     // rays queued once per candidate instance outgrew the host's bound on the shadow queue (a scene whose
     // instance boxes overlap many times over): this scene goes back to whole rays and the tiles are rendered again
@@ -1584,14 +1587,41 @@ int fjgpu_render_tiles(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *
     fprintf(stderr, "fjgpu: shadow queue overflow with rays split per candidate instance: rendering the tiles again without the split, "
         "which stays off for this scene (option split_shadow)\n");
     sc->split_shadow = false;
-    e = render_tiles_once(sc, r, tile_ids, n_tiles, d_fb, hip_stream, stats);
+    e = render_tiles_once(sc, r, tile_ids, n_tiles, d_fb, hip_stream, stats, sv);
   }
   if (!e) sc->render_calls++;
   return e;
 }
 
-static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
+int fjgpu_render_tiles(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
     float *d_fb, void *hip_stream, fjgpu_stats *stats)
+{
+  if (!sc || !r || !d_fb) return fail(FJGPU_EINVAL, "null argument");
+  return render_tiles_retrying(sc, r, tile_ids, n_tiles, d_fb, hip_stream, stats, nullptr);
+}
+
+int fjgpu_render_tiles_variance(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
+    float *d_fb, const float *d_albedo, float albedo_floor, float *d_variance, void *hip_stream, fjgpu_stats *stats)
+{
+  const std::string f = "fjgpu_render_tiles_variance";
+  if (!sc || !r || !d_fb || !d_variance) return fail(FJGPU_EINVAL, f + ": null argument (scene, render, framebuffer and variance are required)");
+  if (d_albedo && !(std::isfinite(albedo_floor) && albedo_floor > 0)) return fail(FJGPU_EINVAL, f + ": albedo_floor must be finite and > 0");
+  if (const char *why = bad_render(r)) return fail(FJGPU_EINVAL, f + ": " + why);
+  const size_t px = (size_t) r->xres * (size_t) r->yres;
+  auto overlaps = [](const float *a, size_t na, const float *b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
+    return a0 < b0 + nb * sizeof(float) && b0 < a0 + na * sizeof(float);
+  };
+  if (overlaps(d_variance, px, d_fb, 4 * px) || (d_albedo && overlaps(d_variance, px, d_albedo, 3 * px)))
+    return fail(FJGPU_EINVAL, f + ": the variance buffer must not overlap the framebuffer or the albedo buffer");
+  // (the adaptive sampler resolves INTERPOLATED samples: they are not independent draws, and their spread is not the estimate's variance)
+  if (r->sampler_type == 1) return fail(FJGPU_EUNSUPPORTED, f + ": the adaptive sampler is not supported (its resolved samples are interpolated, not independent)");
+  const SampleVarianceOut sv = {d_variance, d_albedo, albedo_floor};
+  return render_tiles_retrying(sc, r, tile_ids, n_tiles, d_fb, hip_stream, stats, &sv);
+}
+
+static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
+    float *d_fb, void *hip_stream, fjgpu_stats *stats, const SampleVarianceOut *sv)
 {
   const bool adaptive = r->sampler_type == 1;          // Renderer::SetSamplerType, src/fj_renderer.cc:487-499
   if (r->sampler_type != 0 && !adaptive) return fail(FJGPU_EINVAL, "unknown sampler_type");
@@ -2080,6 +2110,13 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
       return launch_resolve(st, rp, sc->d_tiles, nb, max_px, sc->d_suv, sc->d_accum, adaptive ? sc->d_afinal : nullptr, d_fb);
     });
     if (rc) break;
+    // fjgpu_render_tiles_variance: the same samples once more, while the batch still holds them
+    if (sv) {
+      rc = timed(st, &acc.resolve_ms, [&]() {
+        return launch_sample_variance(st, rp, sc->d_tiles, nb, max_px, sc->d_suv, sc->d_accum, sv->albedo, sv->albedo_floor, sv->variance);
+      });
+      if (rc) break;
+    }
     DCounters hc;
     if (hipMemcpyAsync(&hc, sc->d_cnt, sizeof(hc), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = -1; break; }
     if (hc.overflow) { sc->split_overflowed = S.shadow_join != nullptr; rc = fail(FJGPU_ENOMEM, "wavefront queue overflow: lower the batch_tiles option"); break; }

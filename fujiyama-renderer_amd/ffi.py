@@ -58,6 +58,11 @@ class AovBuffers(C.Structure):         # fjgpu_aov_buffers: DEVICE pointers, 0 =
     _fields_ = [(n, C.c_void_p) for n in ("depth", "position", "normal", "uv", "ids", "coverage")]
 
 
+# fjgpu_render_tiles_variance: scene, render, tile_ids, n_tiles, d_framebuffer, d_albedo, albedo_floor, d_variance, hip_stream, stats
+RENDER_TILES_VARIANCE_ARGTYPES = [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                  C.c_void_p, C.POINTER(GpuStats)]
+
+
 class DenoiseDesc(C.Structure):       # fjgpu_denoise_desc
     _fields_ = [
         ("xres", C.c_int32), ("yres", C.c_int32),

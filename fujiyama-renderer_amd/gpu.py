@@ -25,6 +25,7 @@ def lib():
         L.fjgpu_tile_rect.argtypes = [C.POINTER(ffi.RenderDesc), C.c_int, C.POINTER(C.c_int32)]
         L.fjgpu_render_tiles.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
+        L.fjgpu_render_tiles_variance.argtypes = ffi.RENDER_TILES_VARIANCE_ARGTYPES
         L.fjgpu_render_frame.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_void_p, C.POINTER(ffi.GpuStats)]
         L.fjgpu_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.POINTER(ffi.GpuStats)]
@@ -115,17 +116,43 @@ class Scene(object):
         _check(lib().fjgpu_render_frame(self._h, C.byref(render), fb.ctypes.data_as(C.c_void_p), C.byref(st)))
         return fb, st
 
-    def render_tiles(self, render, tile_ids, d_framebuffer_ptr, stream=None):
-        """Listed tiles into a DEVICE framebuffer (raw pointer, e.g. torch data_ptr())."""
+    def render_tiles(self, render, tile_ids, d_framebuffer_ptr, stream=None, variance=None, albedo=None, albedo_floor=None):
+        """Listed tiles into a DEVICE framebuffer (raw pointer, e.g. torch data_ptr()).  variance: a raw pointer to a DEVICE [H, W]
+        float32 buffer that takes the sample variance of the listed tiles' pixels (include/fjgpu.h: fjgpu_render_tiles_variance), under
+        the DEVICE [H, W, 3] float32 `albedo` (raw pointer) where one is given; albedo_floor None: ALBEDO_FLOOR.  Without `variance` the
+        call is fjgpu_render_tiles."""
         st = ffi.GpuStats()
         if tile_ids is None:
             ids_p, n = None, 0
         else:
             ids = np.ascontiguousarray(tile_ids, dtype=np.int32)
             ids_p, n = ids.ctypes.data_as(C.c_void_p), len(ids)
-        _check(lib().fjgpu_render_tiles(self._h, C.byref(render), ids_p, n, C.c_void_p(d_framebuffer_ptr),
-                                        C.c_void_p(stream or 0), C.byref(st)))
+        if variance is None:
+            if albedo is not None:
+                raise ValueError("albedo is the variance output's: pass variance too")
+            _check(lib().fjgpu_render_tiles(self._h, C.byref(render), ids_p, n, C.c_void_p(d_framebuffer_ptr),
+                                            C.c_void_p(stream or 0), C.byref(st)))
+        else:
+            floor = ALBEDO_FLOOR if albedo_floor is None else albedo_floor
+            _check(lib().fjgpu_render_tiles_variance(self._h, C.byref(render), ids_p, n, C.c_void_p(d_framebuffer_ptr),
+                                                     C.c_void_p(albedo or 0), C.c_float(float(floor)), C.c_void_p(variance),
+                                                     C.c_void_p(stream or 0), C.byref(st)))
         return st
+
+    def render_frame_variance(self, render, albedo=None, albedo_floor=None):
+        """All tiles with the sample variance (include/fjgpu.h: fjgpu_render_tiles_variance) -> numpy [H, W, 4] float32, numpy [H, W]
+        float32, GpuStats.  albedo: [H, W, 3] (numpy or device tensor, Scene.render_aov_albedo's): the variance is that of the luminance
+        of the samples divided by max(albedo, albedo_floor) of their pixel; albedo_floor None: ALBEDO_FLOOR."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        hw = (render.yres, render.xres)
+        fb = torch.zeros(hw + (4,), dtype=torch.float32, device=dev)
+        var = torch.zeros(hw, dtype=torch.float32, device=dev)
+        a = _device_tensor(albedo, "albedo", torch.float32, 3, dev, hw)
+        torch.cuda.synchronize(dev)          # uploads and fills ran on torch's stream
+        st = self.render_tiles(render, None, fb.data_ptr(), variance=var.data_ptr(), albedo=None if a is None else a.data_ptr(),
+                               albedo_floor=albedo_floor)
+        return fb.cpu().numpy(), var.cpu().numpy(), st
 
     def trace(self, group, rays):
         """Closest hits of rays [n, 8] (orig, dir, tmin, tmax) -> t [n], ids [n, 2], uv [n, 2], stats."""
@@ -187,7 +214,7 @@ class Scene(object):
             _check(lib().fjgpu_render_aov(self._h, C.byref(render), ids_p, n, C.byref(bufs), C.c_void_p(stream or 0), C.byref(st)))
         return tensors, st
 
-    def render_denoised(self, render, keep_inputs=False, stream=None, demodulate=False, variance_guided=False, **kw):
+    def render_denoised(self, render, keep_inputs=False, stream=None, demodulate=False, variance_guided=False, variance="spatial", **kw):
         """A beauty frame, its feature buffers and the denoiser (include/fjgpu.h: fjgpu_denoise) in one go, everything on the device:
         render_tiles into a device framebuffer, render_aov(want=("position", "normal", "ids")), denoise over the render region; the
         only copy to the host is the result's.  -> (numpy [H, W, 4] float32, info) with info["beauty_stats"], info["aov_stats"],
@@ -200,19 +227,33 @@ class Scene(object):
         info["albedo_floor"] is the value used (denoise()'s albedo_floor).  variance_guided=True filters with denoise_variance()
         (include/fjgpu.h: fjgpu_denoise_variance, the variance estimated from the frame; `kw` are then its parameters) in place of
         denoise(); it combines with demodulate, and the derived sigma_position is SIGMA_POSITION_FRACTION_VARIANCE of the diagonal.  info["sigma_luminance"] is the value used and, with keep_inputs, info["variance"] the
-        [H, W] variance of the last iteration."""
+        [H, W] variance of the last iteration.  variance="samples" (with variance_guided): the filter's input variance is the beauty pass's
+        sample variance (include/fjgpu.h: fjgpu_render_tiles_variance) in place of the spatial estimate -- the AOV call then runs BEFORE
+        the beauty pass, so that with demodulate the variance is taken under the albedo; with keep_inputs info["variance_in"] is that
+        [H, W] variance.  variance="spatial", the default, is the path described above."""
         import torch
         dev = torch.device("cuda", self._device)
         region = tuple(int(v) for v in render.region)
         if "region" in kw:
             raise ValueError("render_denoised filters the render region of `render`")
+        if variance not in ("spatial", "samples"):
+            raise ValueError("variance is \"spatial\" or \"samples\", not %r" % (variance,))
+        if variance == "samples" and not variance_guided:
+            raise ValueError("variance=\"samples\" is the variance-guided filter's input: variance_guided=True")
         fb = torch.zeros((render.yres, render.xres, 4), dtype=torch.float32, device=dev)
         torch.cuda.synchronize(dev)          # the fill ran on torch's stream
-        st_beauty = self.render_tiles(render, None, fb.data_ptr(), stream=stream)
-        if demodulate:
-            aov, st_aov = self._render_aov_device(render, want=("position", "normal", "ids", "albedo"), stream=stream, names=AOV_ALL)
+        want = ("position", "normal", "ids") + (("albedo",) if demodulate else ())
+        var_in = None
+        if variance == "samples":
+            aov, st_aov = self._render_aov_device(render, want=want, stream=stream, names=AOV_ALL if demodulate else AOV_NAMES)
+            var_in = torch.zeros((render.yres, render.xres), dtype=torch.float32, device=dev)
+            torch.cuda.synchronize(dev)
+            st_beauty = self.render_tiles(render, None, fb.data_ptr(), stream=stream, variance=var_in.data_ptr(),
+                                          albedo=aov["albedo"].data_ptr() if demodulate else None,
+                                          albedo_floor=kw.get("albedo_floor", ALBEDO_FLOOR))
         else:
-            aov, st_aov = self._render_aov_device(render, want=("position", "normal", "ids"), stream=stream)
+            st_beauty = self.render_tiles(render, None, fb.data_ptr(), stream=stream)
+            aov, st_aov = self._render_aov_device(render, want=want, stream=stream, names=AOV_ALL if demodulate else AOV_NAMES)
         if kw.get("sigma_position") is None:
             x0, y0, x1, y1 = region
             pos = aov["position"][y0:y1, x0:x1].reshape(-1, 3)
@@ -236,6 +277,10 @@ class Scene(object):
             info["sigma_luminance"] = kw.setdefault("sigma_luminance", SIGMA_LUMINANCE)
             if "variance" in kw or "return_variance" in kw or "variance_out" in kw:
                 raise ValueError("render_denoised estimates the variance from its own frame")
+            if var_in is not None:
+                kw["variance"] = var_in
+                if keep_inputs:
+                    info["variance_in"] = var_in.cpu().numpy()
             res = denoise_variance(fb, aov["normal"], aov["position"], aov["ids"], region=region, device=self._device, stream=stream,
                                    out=fb, return_variance=bool(keep_inputs), **kw)
             if keep_inputs:
@@ -675,16 +720,22 @@ class TemporalDenoiser(object):
     only copy to the host is the result's.  `params` are temporal_accumulate's alpha_min, max_history, tol_position, cos_normal,
     min_history_variance and denoise_variance's sigma_luminance, iterations, sigma_normal, sigma_position, stop_at_ids, albedo_floor.
     tol_position / sigma_position not given: TOL_POSITION_FRACTION / SIGMA_POSITION_FRACTION_VARIANCE of the diagonal of the bounding
-    box of the first frame's foreground (a frame without foreground switches the terms off).  The limits are the entry's: static scene,
+    box of the first frame's foreground (a frame without foreground switches the terms off).  variance="samples": the beauty pass's sample
+    variance (Scene.render_tiles(variance=...), the AOV call in front of it) is temporal_accumulate's variance_spatial -- the fallback for
+    short histories -- and the spatial estimate is not run (info["estimate_stats"] is None); "spatial", the default, estimates it from
+    the frame.  The limits are the entry's: static scene,
     static camera per frame, fixed-grid sampler; frames from one and the same camera are identical and gain nothing."""
 
     _TEMPORAL = ("alpha_min", "max_history", "tol_position", "cos_normal", "min_history_variance")
     _FILTER = ("sigma_luminance", "iterations", "sigma_normal", "sigma_position", "stop_at_ids")
 
-    def __init__(self, scene, render, demodulate=True, stream=None, **params):
+    def __init__(self, scene, render, demodulate=True, stream=None, variance="spatial", **params):
         for k in params:
             if k not in self._TEMPORAL + self._FILTER + ("albedo_floor",):
                 raise ValueError("unknown parameter %r" % k)
+        if variance not in ("spatial", "samples"):
+            raise ValueError("variance is \"spatial\" or \"samples\", not %r" % (variance,))
+        self.variance = variance
         self.scene, self.render_desc, self.demodulate, self.stream = scene, render.copy(), bool(demodulate), stream
         self.params = dict(params)
         self.albedo_floor = float(self.params.pop("albedo_floor", ALBEDO_FLOOR))
@@ -701,7 +752,8 @@ class TemporalDenoiser(object):
         """one frame -> (numpy [H, W, 4] float32, info).  camera: an ffi.CameraDesc, or a dict of Scene.set_camera's overrides, or None
         (the scene's current camera).  info: "beauty_stats", "aov_stats", "estimate_stats", "temporal_stats", "denoise_stats" (GpuStats),
         "tol_position", "sigma_position" (the values used), "frame" (0 for the first of a sequence) and, with keep_inputs, "beauty",
-        "aov", "accumulated", "history_length" [H, W] and "variance" [H, W] (the temporal pass's) as numpy copies."""
+        "aov", "variance_spatial" [H, W] (the temporal pass's fallback: the estimate, or the sample variance), "accumulated",
+        "history_length" [H, W] and "variance" [H, W] (the temporal pass's) as numpy copies."""
         import torch
         sc, r = self.scene, self.render_desc
         dev = torch.device("cuda", sc._device)
@@ -711,9 +763,17 @@ class TemporalDenoiser(object):
         view = sc.view(r)            # (the refusals of the AOV pass, before anything is rendered)
         fb = torch.zeros((r.yres, r.xres, 4), dtype=torch.float32, device=dev)
         torch.cuda.synchronize(dev)          # the fill ran on torch's stream
-        st_beauty = sc.render_tiles(r, None, fb.data_ptr(), stream=self.stream)
         want = ("position", "normal", "ids") + (("albedo",) if self.demodulate else ())
-        aov, st_aov = sc._render_aov_device(r, want=want, stream=self.stream, names=AOV_ALL if self.demodulate else AOV_NAMES)
+        var_s = None
+        if self.variance == "samples":       # (the AOV call first: the sample variance is taken under its albedo)
+            aov, st_aov = sc._render_aov_device(r, want=want, stream=self.stream, names=AOV_ALL if self.demodulate else AOV_NAMES)
+            var_s = torch.zeros((r.yres, r.xres), dtype=torch.float32, device=dev)
+            torch.cuda.synchronize(dev)
+            st_beauty = sc.render_tiles(r, None, fb.data_ptr(), stream=self.stream, variance=var_s.data_ptr(),
+                                        albedo=aov["albedo"].data_ptr() if self.demodulate else None, albedo_floor=self.albedo_floor)
+        else:
+            st_beauty = sc.render_tiles(r, None, fb.data_ptr(), stream=self.stream)
+            aov, st_aov = sc._render_aov_device(r, want=want, stream=self.stream, names=AOV_ALL if self.demodulate else AOV_NAMES)
         p = self.params
         if "tol_position" not in p or p.get("sigma_position") is None:
             x0, y0, x1, y1 = region
@@ -729,9 +789,11 @@ class TemporalDenoiser(object):
         tkw = {k: p[k] for k in self._TEMPORAL if k in p}
         fkw = {k: p[k] for k in self._FILTER if k in p}
         albedo = aov.get("albedo")
-        var_s, st_est = _estimate_variance_device(fb, aov["normal"], aov["position"], aov["ids"], albedo, self.albedo_floor, region,
-                                                  fkw.get("sigma_normal", SIGMA_NORMAL), fkw["sigma_position"], fkw.get("stop_at_ids", True),
-                                                  sc._device, self.stream)
+        st_est = None                        # (variance="samples": no estimate, the beauty pass wrote var_s)
+        if var_s is None:
+            var_s, st_est = _estimate_variance_device(fb, aov["normal"], aov["position"], aov["ids"], albedo, self.albedo_floor, region,
+                                                      fkw.get("sigma_normal", SIGMA_NORMAL), fkw["sigma_position"], fkw.get("stop_at_ids", True),
+                                                      sc._device, self.stream)
         prev = self._prev
         hist, var_t, st_tmp = temporal_accumulate(
             fb, aov["position"], aov["normal"], aov["ids"], albedo=albedo, variance_spatial=var_s,
@@ -746,6 +808,7 @@ class TemporalDenoiser(object):
         if keep_inputs:
             info["beauty"] = fb.cpu().numpy()
             info["aov"] = {name: t.cpu().numpy() for name, t in aov.items()}
+            info["variance_spatial"] = var_s.cpu().numpy()
             info["accumulated"] = hist["color"].cpu().numpy()
             info["history_length"] = hist["length"].cpu().numpy()
             info["variance"] = var_t.cpu().numpy()

@@ -96,6 +96,31 @@ int fjgpu_render_tiles(fjgpu_scene *scene, const fj_render_desc *render,
     const int32_t *tile_ids, int n_tiles,
     float *d_framebuffer, void *hip_stream, fjgpu_stats *stats);
 
+/* fjgpu_render_tiles plus a SAMPLE VARIANCE buffer: for every pixel of the listed tiles the variance of the luminance of the pixel's
+ * filtered estimate, taken from the per-sample radiances the beauty pass holds when it resolves a batch -- the variance_in of
+ * fjgpu_denoise_variance and the variance_spatial of fjgpu_denoise_temporal from the samples themselves, not from the finished frame.
+ * The framebuffer, the ray counts and the stats are fjgpu_render_tiles's (same body, same launches; one more kernel per batch right after
+ * the resolve, its time in resolve_ms).  csrc/device/fjgpu_sample_var_math.h is the one source of the arithmetic.  For pixel p, over the
+ * window samples s the pixel filter reads for p (reconstruct_image / apply_pixel_filter: rate + 2 margin per axis), sums in f64:
+ *   w_s = the filter's Gaussian weight of s for p, exp(-2 (xx xx + yy yy)) in f64;
+ *   l_s = l(d), f32, l as in fjgpu_denoise_variance; d = the sample's rgb, or with d_albedo d_k = x_k / a'_k per channel with
+ *         a'_k = albedo[p]_k > albedo_floor ? albedo[p]_k : albedo_floor -- the PIXEL's albedo (fjgpu_denoise_albedo's statements), so the
+ *         result describes the demodulated luminance those two consumers work with;
+ *   pass 1: S0 = sum w, S1 = sum w l, m = S1 / S0;    pass 2, same samples and weights: S2 = sum w (l - m)^2, Q = sum w^2;
+ *   e = Q / S0^2 (1 / n for n equal weights);   V = (S2 / S0) e / (1 - e) -- for n equal weights the unbiased sample variance divided by n;
+ *   V = 0 where e >= 1 (one sample); rounded to f32 once; a V that is negative or not finite (a non-finite sample) is written as 0.f.
+ * d_variance is a DEVICE [yres][xres] f32 buffer; pixels of tiles not listed are left untouched in it.  d_albedo (may be NULL; then
+ * albedo_floor is ignored) is a DEVICE [yres][xres][3] f32 buffer (fjgpu_render_aov_albedo's) of which only listed tiles' pixels are read.
+ * Scenes with motion, a moving camera and area lights are served: their accumulators are the same.  If the call has to be repeated because
+ * split shadow rays overflowed their queue (see "split_shadow"), the variance is written again with the frame.
+ * Errors, before any device work, every message starting "fjgpu_render_tiles_variance:": FJGPU_EINVAL for a NULL scene, render, framebuffer
+ * or variance, for an albedo_floor that is not finite and > 0 where d_albedo is set, and for a d_variance that overlaps the framebuffer or
+ * the albedo; FJGPU_EUNSUPPORTED for the adaptive sampler (its resolved samples are interpolated, not independent).  Everything else is
+ * fjgpu_render_tiles's. */
+int fjgpu_render_tiles_variance(fjgpu_scene *scene, const fj_render_desc *render, const int32_t *tile_ids, int n_tiles,
+    float *d_framebuffer, const float *d_albedo /* DEVICE [yres][xres][3] or NULL */, float albedo_floor,
+    float *d_variance /* DEVICE [yres][xres] f32 */, void *hip_stream, fjgpu_stats *stats);
+
 /* Batch callback.  fjgpu_render_tiles cuts its tile list into BATCHES (as many tiles as the wavefront
  * queues hold: a whole 1080p / 64 spp frame is one batch, option "batch_tiles"); `fn` is called on the
  * calling host thread each time a batch is complete on the device -- the tiles' pixels are final in the
