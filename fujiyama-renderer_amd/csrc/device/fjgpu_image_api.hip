@@ -294,12 +294,14 @@ int fjgpu_denoise_variance(int device, const fjgpu_denoise_desc *d, float sigma_
 }
 
 // ---- temporal accumulation (fjgpu_temporal.hip, fjgpu_temporal_math.h).  One launch, no scratch: every refusal is decided before a device call.
-int fjgpu_denoise_temporal(int device, const fjgpu_temporal_desc *d, const float *color, const float *position, const float *normal,
-    const int32_t *ids, const float *albedo, const float *variance_spatial, const fjgpu_view *prev_view, const float *prev_position,
-    const float *prev_normal, const int32_t *prev_ids, const fjgpu_temporal_history *prev, const fjgpu_temporal_history *next,
-    float *variance_out, void *hip_stream, fjgpu_stats *stats)
+// The clamp's refusals come after those of the unclamped entry, which keeps its order.
+// `name`: the entry point called; `clamp` NULL: fjgpu_denoise_temporal, whichever of the two it was
+static int temporal(const char *name, int device, const fjgpu_temporal_desc *d, const fjgpu_temporal_clamp *clamp, const float *color,
+    const float *position, const float *normal, const int32_t *ids, const float *albedo, const float *variance_spatial,
+    const fjgpu_view *prev_view, const float *prev_position, const float *prev_normal, const int32_t *prev_ids,
+    const fjgpu_temporal_history *prev, const fjgpu_temporal_history *next, float *variance_out, void *hip_stream, fjgpu_stats *stats)
 {
-  ImageCall call("fjgpu_denoise_temporal", hip_stream);
+  ImageCall call(name, hip_stream);
   const std::string &f = call.f;
   if (!d || !color) return fail(FJGPU_EINVAL, f + ": null argument (desc and color are required)");
   if (!position || !normal || !ids) return fail(FJGPU_EINVAL, f + ": null guide (position, normal and ids are required: without them there is nothing to reproject)");
@@ -332,6 +334,18 @@ int fjgpu_denoise_temporal(int device, const fjgpu_temporal_desc *d, const float
         if (tp_overlap(outs[a].p, outs[a].n, outs[b].p, outs[b].n)) return fail(FJGPU_EINVAL, f + ": output buffers (next, variance_out) overlap each other");
     }
   }
+  if (clamp) {
+    if (clamp->radius < 1 || clamp->radius > FJ_TP_CLAMP_MAX_RADIUS) return fail(FJGPU_EINVAL, f + ": clamp radius must be 1..3");
+    if (!(std::isfinite(clamp->gamma) && clamp->gamma > 0.f)) return fail(FJGPU_EINVAL, f + ": clamp gamma must be finite and > 0");
+    const size_t px = (size_t) d->xres * (size_t) d->yres * sizeof(float);
+    const struct { const void *p; size_t n; } others[16] = {{color, 4 * px}, {position, 3 * px}, {normal, 3 * px}, {ids, 4 * px}, {albedo, 3 * px},
+        {variance_spatial, px}, {prev ? prev_position : nullptr, 3 * px}, {prev ? prev_normal : nullptr, 3 * px}, {prev ? prev_ids : nullptr, 4 * px},
+        {prev ? prev->color : nullptr, 4 * px}, {prev ? prev->moments : nullptr, 2 * px}, {prev ? prev->length : nullptr, px},
+        {next->color, 4 * px}, {next->moments, 2 * px}, {next->length, px}, {variance_out, px}};
+    for (int b = 0; b < 16; b++)
+      if (tp_overlap(clamp->amount, px, others[b].p, others[b].n))
+        return fail(FJGPU_EINVAL, f + ": the clamp's amount overlaps an input, prev, next or variance_out");
+  }
   if (const int e = call.open(device)) return e;
 
   TpParams k;
@@ -359,10 +373,34 @@ int fjgpu_denoise_temporal(int device, const fjgpu_temporal_desc *d, const float
   call.start(2);
   if (!call.rc) {
     call.mark(0);
-    call.rc = launch_tp_accumulate(call.st, k, B);
+    if (clamp) {
+      TpClamp c;
+      c.radius = clamp->radius; c.stop_at_ids = clamp->stop_at_ids ? 1 : 0; c.gamma = clamp->gamma; c.amount = clamp->amount;
+      call.rc = launch_tp_accumulate_clamped(call.st, k, B, c);
+    } else {
+      call.rc = launch_tp_accumulate(call.st, k, B);
+    }
     call.mark(1);
   }
   return call.finish(stats, 1, {0, 1}, {}, {0, 1});
+}
+
+int fjgpu_denoise_temporal(int device, const fjgpu_temporal_desc *d, const float *color, const float *position, const float *normal,
+    const int32_t *ids, const float *albedo, const float *variance_spatial, const fjgpu_view *prev_view, const float *prev_position,
+    const float *prev_normal, const int32_t *prev_ids, const fjgpu_temporal_history *prev, const fjgpu_temporal_history *next,
+    float *variance_out, void *hip_stream, fjgpu_stats *stats)
+{
+  return temporal("fjgpu_denoise_temporal", device, d, nullptr, color, position, normal, ids, albedo, variance_spatial, prev_view, prev_position,
+                  prev_normal, prev_ids, prev, next, variance_out, hip_stream, stats);
+}
+
+int fjgpu_denoise_temporal_clamped(int device, const fjgpu_temporal_desc *d, const fjgpu_temporal_clamp *clamp, const float *color,
+    const float *position, const float *normal, const int32_t *ids, const float *albedo, const float *variance_spatial,
+    const fjgpu_view *prev_view, const float *prev_position, const float *prev_normal, const int32_t *prev_ids,
+    const fjgpu_temporal_history *prev, const fjgpu_temporal_history *next, float *variance_out, void *hip_stream, fjgpu_stats *stats)
+{
+  return temporal("fjgpu_denoise_temporal_clamped", device, d, clamp, color, position, normal, ids, albedo, variance_spatial, prev_view,
+                  prev_position, prev_normal, prev_ids, prev, next, variance_out, hip_stream, stats);
 }
 
 }  // extern "C"

@@ -4,7 +4,9 @@
 //
 // ONE source for the device kernel (fjgpu_temporal.hip: k_tp_accumulate), for the host twin the CPU tests run (tools/temporal_host.cc) and
 // for tests/temporal_model.py, which restates it in numpy.  f32 under -ffp-contract=off, every sum left to right; the projection alone is
-// f64.  A pixel is one call of fj_tp_pixel: kernel and twin differ in who calls it, not in a statement of it.
+// f64.  A pixel is one call of fj_tp_pixel -- fj_tp_fetch, then fj_tp_finish --: kernel and twin differ in who calls it, not in a
+// statement of it.  fjgpu_denoise_temporal_clamped puts fj_tp_clamp between the two (fj_tp_pixel_clamped; k_tp_accumulate_clamped and
+// the twin's fj_denoise_temporal_clamped_host; tests/temporal_clamp_model.py restates it).
 //
 //   projection of the world point P through the view (world_to_camera M, rows of a 3 x 4 matrix; uv_size; xres, yres), f64:
 //     c_k = ((M[4k] P.x + M[4k+1] P.y) + M[4k+2] P.z) + M[4k+3];      visible only if c.z < 0
@@ -17,6 +19,11 @@
 //   blend       n = min(H_len + 1, max_history), alpha = max(1.f / n, alpha_min), X' = H + alpha (X - H) for X in {C (4), L, L L}; len' = n
 //   no history  C' = C, m1 = L, m2 = L L, len' = 1
 //   variance    v = max(0, m2' - m1' m1'); where len' < min_history_variance and there is a spatial variance: that
+//   clamp       (the clamped entry, pixels with a history, after H /= wsum) taps q = p + (dx, dy), dy = -r..r outer, dx = -r..r inner, of
+//               the CURRENT frame; a tap counts if it lies in the region and (stop_at_ids) ids[q][0] == ids[p][0].  For X in {C_q (4), L_q}:
+//               cnt += 1.f, s1 += X_q, m = s1 / cnt; then over the same taps d = X_q - m, s2 += d d, sd = sqrtf(s2 / cnt);
+//               lo = m - gamma sd, hi = m + gamma sd;  H' = H < lo ? lo : (H > hi ? hi : H) for the colour and, against L's box, for h1;
+//               h2' = h2 where h1' == h1, else (h2 - h1 h1) + h1' h1';  amount = max |H' - H| over r, g, b;  blend and variance from H'
 #ifndef FJGPU_TEMPORAL_MATH_H
 #define FJGPU_TEMPORAL_MATH_H
 
@@ -77,19 +84,33 @@ FJ_DN_FN bool fj_tp_project(const TpParams &k, float px, float py, float pz, dou
 
 FJ_DN_FN float fj_tp_blend(float h, float x, float alpha) { return h + alpha * (x - h); }
 
-// the region pixel (x, y)
-FJ_DN_FN void fj_tp_pixel(const TpParams &k, const TpBuffers &B, int x, int y)
+// what the fetch leaves of a pixel: the current colour and luminance and -- where have -- the history at its projection, already divided
+// by the valid weight
+struct TpFetched {
+  tp_v4f C;
+  float L;
+  bool have;                       // wsum > FJ_TP_MIN_WEIGHT
+  float hr, hg, hb, ha, h1, h2, hl;
+};
+
+// L of the pixel at index `at` whose colour is C: the luminance of every statement above, and of the clamp's window
+FJ_DN_FN float fj_tp_luminance(const TpParams &k, const TpBuffers &B, size_t at, const tp_v4f &C)
 {
-  const size_t at = (size_t) y * (size_t) k.xres + (size_t) x;
-  const tp_v4f C = *(const tp_v4f *) (B.color + 4 * at);
   float dr = C.x, dg = C.y, db = C.z;
   if (B.albedo) {
     dr = fj_dn_demodulate(C.x, fj_dn_albedo_clamp(B.albedo[3 * at], k.albedo_floor));
     dg = fj_dn_demodulate(C.y, fj_dn_albedo_clamp(B.albedo[3 * at + 1], k.albedo_floor));
     db = fj_dn_demodulate(C.z, fj_dn_albedo_clamp(B.albedo[3 * at + 2], k.albedo_floor));
   }
-  const float L = fj_dnv_luminance(dr, dg, db);
-  const float L2 = L * L;
+  return fj_dnv_luminance(dr, dg, db);
+}
+
+// the region pixel (x, y) up to and including H /= wsum
+FJ_DN_FN TpFetched fj_tp_fetch(const TpParams &k, const TpBuffers &B, int x, int y)
+{
+  const size_t at = (size_t) y * (size_t) k.xres + (size_t) x;
+  const tp_v4f C = *(const tp_v4f *) (B.color + 4 * at);
+  const float L = fj_tp_luminance(k, B, at, C);
   const int32_t I = B.ids[4 * at];
   float wsum = 0.f, hr = 0.f, hg = 0.f, hb = 0.f, ha = 0.f, h1 = 0.f, h2 = 0.f, hl = 0.f;
   if (B.prev_color && I >= 0) {
@@ -130,17 +151,33 @@ FJ_DN_FN void fj_tp_pixel(const TpParams &k, const TpBuffers &B, int x, int y)
       }
     }
   }
+  TpFetched F;
+  F.C = C; F.L = L;
+  F.have = wsum > FJ_TP_MIN_WEIGHT;
+  F.hr = hr; F.hg = hg; F.hb = hb; F.ha = ha; F.h1 = h1; F.h2 = h2; F.hl = hl;
+  if (F.have) {
+    F.hr = hr / wsum; F.hg = hg / wsum; F.hb = hb / wsum; F.ha = ha / wsum; F.h1 = h1 / wsum; F.h2 = h2 / wsum; F.hl = hl / wsum;
+  }
+  return F;
+}
+
+// blend, variance and the stores of the region pixel (x, y) from what was fetched (and, in the clamped pass, rectified)
+FJ_DN_FN void fj_tp_finish(const TpParams &k, const TpBuffers &B, int x, int y, const TpFetched &F)
+{
+  const size_t at = (size_t) y * (size_t) k.xres + (size_t) x;
+  const tp_v4f C = F.C;
+  const float L = F.L;
+  const float L2 = L * L;
   tp_v4f O = C;
   float m1 = L, m2 = L2, n = 1.f;
-  if (wsum > FJ_TP_MIN_WEIGHT) {
-    hr = hr / wsum; hg = hg / wsum; hb = hb / wsum; ha = ha / wsum; h1 = h1 / wsum; h2 = h2 / wsum; hl = hl / wsum;
-    const float n1 = hl + 1.f;
+  if (F.have) {
+    const float n1 = F.hl + 1.f;
     n = n1 < k.max_history ? n1 : k.max_history;
     const float r = 1.f / n;
     const float alpha = r > k.alpha_min ? r : k.alpha_min;
-    O.x = fj_tp_blend(hr, C.x, alpha); O.y = fj_tp_blend(hg, C.y, alpha); O.z = fj_tp_blend(hb, C.z, alpha); O.w = fj_tp_blend(ha, C.w, alpha);
-    m1 = fj_tp_blend(h1, L, alpha);
-    m2 = fj_tp_blend(h2, L2, alpha);
+    O.x = fj_tp_blend(F.hr, C.x, alpha); O.y = fj_tp_blend(F.hg, C.y, alpha); O.z = fj_tp_blend(F.hb, C.z, alpha); O.w = fj_tp_blend(F.ha, C.w, alpha);
+    m1 = fj_tp_blend(F.h1, L, alpha);
+    m2 = fj_tp_blend(F.h2, L2, alpha);
   }
   *(tp_v4f *) (B.next_color + 4 * at) = O;
   B.next_moments[2 * at] = m1;
@@ -152,6 +189,113 @@ FJ_DN_FN void fj_tp_pixel(const TpParams &k, const TpBuffers &B, int x, int y)
     if (B.variance_spatial && n < k.min_history_variance) v = B.variance_spatial[at];
     B.variance_out[at] = v;
   }
+}
+
+// ---- the history rectification of fjgpu_denoise_temporal_clamped (variance clipping, Salvi 2016), between fetch and finish.
+// Its window is read as RECORDS of FJ_TP_REC words -- C.r C.g C.b C.a, L, the bits of ids[q][0] --, one per pixel, through a pointer to
+// the centre's record and the strides of a row and of a pixel in words: the kernel points it into its LDS tile, the twin into the records
+// of the caller's frame.  fj_tp_record writes one; a record outside the region is never written and never read.
+#define FJ_TP_REC 6
+#define FJ_TP_CLAMP_MAX_RADIUS 3
+
+// what fjgpu_temporal_clamp says, for the kernel
+struct TpClamp {
+  int32_t radius, stop_at_ids;
+  float gamma;
+  float *amount;                   // pixel (0, 0) of [yres][xres], or null
+};
+
+FJ_DN_FN void fj_tp_record(const TpParams &k, const TpBuffers &B, int x, int y, float *rec)
+{
+  const size_t at = (size_t) y * (size_t) k.xres + (size_t) x;
+  const tp_v4f C = *(const tp_v4f *) (B.color + 4 * at);
+  const int32_t I = B.ids[4 * at];
+  rec[0] = C.x; rec[1] = C.y; rec[2] = C.z; rec[3] = C.w;
+  rec[4] = fj_tp_luminance(k, B, at, C);
+  __builtin_memcpy(rec + 5, &I, 4);
+}
+
+FJ_DN_FN float fj_tp_clip(float h, float lo, float hi) { return h < lo ? lo : (h > hi ? hi : h); }
+
+// whether the tap at (qx, qy), whose record is `q`, counts in the window of a pixel with id I; the record of a tap outside the region is not read
+FJ_DN_FN bool fj_tp_tap_counts(const TpParams &k, int stop_at_ids, int32_t I, const float *q, int qx, int qy)
+{
+  if (qx < k.x0 || qx >= k.x1 || qy < k.y0 || qy >= k.y1) return false;
+  int32_t qi;
+  __builtin_memcpy(&qi, q + 5, 4);
+  return !stop_at_ids || qi == I;
+}
+
+// the pixel (x, y), which has a history: F's colour and moments clipped to the box of the window around `centre`; returns the amount
+template <int radius>
+FJ_DN_FN float fj_tp_clamp(const TpParams &k, float gamma, int stop_at_ids, const float *centre, int row, int px, int x, int y,
+    TpFetched &F)
+{
+  int32_t I;
+  __builtin_memcpy(&I, centre + 5, 4);
+  float cnt = 0.f, s1[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, s2[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, m[5];
+#pragma unroll
+  for (int dy = -radius; dy <= radius; dy++) {
+#pragma unroll
+    for (int dx = -radius; dx <= radius; dx++) {
+      const float *q = centre + dy * row + dx * px;
+      if (fj_tp_tap_counts(k, stop_at_ids, I, q, x + dx, y + dy)) {
+        cnt += 1.f;
+#pragma unroll
+        for (int c = 0; c < 5; c++) s1[c] += q[c];
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 5; c++) m[c] = s1[c] / cnt;
+#pragma unroll
+  for (int dy = -radius; dy <= radius; dy++) {
+#pragma unroll
+    for (int dx = -radius; dx <= radius; dx++) {
+      const float *q = centre + dy * row + dx * px;
+      if (fj_tp_tap_counts(k, stop_at_ids, I, q, x + dx, y + dy)) {
+#pragma unroll
+        for (int c = 0; c < 5; c++) {
+          const float d = q[c] - m[c];
+          s2[c] += d * d;
+        }
+      }
+    }
+  }
+  float lo[5], hi[5];
+#pragma unroll
+  for (int c = 0; c < 5; c++) {
+    const float sd = sqrtf(s2[c] / cnt);
+    lo[c] = m[c] - gamma * sd;
+    hi[c] = m[c] + gamma * sd;
+  }
+  const float hr = fj_tp_clip(F.hr, lo[0], hi[0]), hg = fj_tp_clip(F.hg, lo[1], hi[1]), hb = fj_tp_clip(F.hb, lo[2], hi[2]);
+  const float ha = fj_tp_clip(F.ha, lo[3], hi[3]);
+  const float h1 = fj_tp_clip(F.h1, lo[4], hi[4]);
+  const float ar = fabsf(hr - F.hr), ag = fabsf(hg - F.hg), ab = fabsf(hb - F.hb);
+  float amount = ar;
+  amount = ag > amount ? ag : amount;
+  amount = ab > amount ? ab : amount;
+  if (h1 != F.h1) F.h2 = (F.h2 - F.h1 * F.h1) + h1 * h1;
+  F.hr = hr; F.hg = hg; F.hb = hb; F.ha = ha; F.h1 = h1;
+  return amount;
+}
+
+// the region pixel (x, y) of fjgpu_denoise_temporal_clamped with c.radius == radius; `centre`, `row`, `px`: its record in the window's records
+template <int radius>
+FJ_DN_FN void fj_tp_pixel_clamped(const TpParams &k, const TpBuffers &B, const TpClamp &c, const float *centre, int row, int px, int x, int y)
+{
+  TpFetched F = fj_tp_fetch(k, B, x, y);
+  float amount = 0.f;
+  if (F.have) amount = fj_tp_clamp<radius>(k, c.gamma, c.stop_at_ids, centre, row, px, x, y, F);
+  if (c.amount) c.amount[(size_t) y * (size_t) k.xres + (size_t) x] = amount;
+  fj_tp_finish(k, B, x, y, F);
+}
+
+// the region pixel (x, y) of fjgpu_denoise_temporal
+FJ_DN_FN void fj_tp_pixel(const TpParams &k, const TpBuffers &B, int x, int y)
+{
+  fj_tp_finish(k, B, x, y, fj_tp_fetch(k, B, x, y));
 }
 
 #endif

@@ -1,18 +1,23 @@
-// temporal_host.cc -- validation tool: fjgpu_denoise_temporal (include/fjgpu.h) as a plain loop over HOST arrays, every pixel through
-// fj_tp_pixel of device/fjgpu_temporal_math.h -- the SAME function k_tp_accumulate calls -- so that tests/test_temporal_cpu.py can hold the
-// arithmetic against its numpy restatement without a GPU.  Built with the ROCm clang++ under -ffp-contract=off.  Not part of the product path.
+// temporal_host.cc -- validation tool: fjgpu_denoise_temporal and fjgpu_denoise_temporal_clamped (include/fjgpu.h) as plain loops over HOST
+// arrays, every pixel through fj_tp_pixel / fj_tp_pixel_clamped of device/fjgpu_temporal_math.h -- the SAME functions k_tp_accumulate and
+// k_tp_accumulate_clamped call -- so that tests/test_temporal_cpu.py and tests/test_temporal_clamp_cpu.py can hold the arithmetic against
+// its numpy restatements without a GPU.  Built with the ROCm clang++ under -ffp-contract=off.  Not part of the product path.
 #include <stdint.h>
 #include <math.h>
 #include <string.h>
+
+#include <vector>
 
 #include "fjgpu.h"
 #include "fjgpu_temporal_math.h"
 
 extern "C" {
 
-// the arguments of fjgpu_denoise_temporal on host memory; 0, or -2 (FJGPU_EINVAL) for what it refuses (the overlap test is the entry's own)
-int fj_denoise_temporal_host(const fjgpu_temporal_desc *d, const float *color, const float *position, const float *normal, const int32_t *ids,
-    const float *albedo, const float *variance_spatial, const fjgpu_view *prev_view, const float *prev_position, const float *prev_normal,
+// the arguments of fjgpu_denoise_temporal_clamped on host memory; 0, or -2 (FJGPU_EINVAL) for what it refuses (the overlap tests are the
+// entry's own).  With a clamp the window's records (fj_tp_record: RGBA, L, id) of the region are written first, as the kernel's blocks
+// write their tiles, and fj_tp_clamp reads them through the strides of the frame.
+int fj_denoise_temporal_clamped_host(const fjgpu_temporal_desc *d, const fjgpu_temporal_clamp *clamp, const float *color, const float *position,
+    const float *normal, const int32_t *ids, const float *albedo, const float *variance_spatial, const fjgpu_view *prev_view, const float *prev_position, const float *prev_normal,
     const int32_t *prev_ids, const fjgpu_temporal_history *prev, const fjgpu_temporal_history *next, float *variance_out)
 {
   if (!d || !color || !position || !normal || !ids) return FJGPU_EINVAL;
@@ -28,6 +33,7 @@ int fj_denoise_temporal_host(const fjgpu_temporal_desc *d, const float *color, c
   if (albedo && !(isfinite(d->albedo_floor) && d->albedo_floor > 0)) return FJGPU_EINVAL;
   if (prev && (prev_view->xres <= 0 || prev_view->yres <= 0)) return FJGPU_EINVAL;
   if (((uintptr_t) color | (uintptr_t) next->color | (uintptr_t) (prev ? prev->color : nullptr)) & 15u) return FJGPU_EINVAL;
+  if (clamp && (clamp->radius < 1 || clamp->radius > FJ_TP_CLAMP_MAX_RADIUS || !(isfinite(clamp->gamma) && clamp->gamma > 0.f))) return FJGPU_EINVAL;
 
   TpParams k;
   memset(&k, 0, sizeof(k));
@@ -50,9 +56,34 @@ int fj_denoise_temporal_host(const fjgpu_temporal_desc *d, const float *color, c
   }
   B.next_color = next->color; B.next_moments = next->moments; B.next_length = next->length;
   B.variance_out = variance_out;
+  if (!clamp) {
+    for (int y = k.y0; y < k.y1; y++)
+      for (int x = k.x0; x < k.x1; x++) fj_tp_pixel(k, B, x, y);
+    return 0;
+  }
+  TpClamp c;
+  c.radius = clamp->radius; c.stop_at_ids = clamp->stop_at_ids ? 1 : 0; c.gamma = clamp->gamma; c.amount = clamp->amount;
+  const int row = k.xres * FJ_TP_REC;
+  std::vector<float> records((size_t) k.yres * (size_t) row);
   for (int y = k.y0; y < k.y1; y++)
-    for (int x = k.x0; x < k.x1; x++) fj_tp_pixel(k, B, x, y);
+    for (int x = k.x0; x < k.x1; x++) fj_tp_record(k, B, x, y, records.data() + (size_t) y * row + (size_t) x * FJ_TP_REC);
+  for (int y = k.y0; y < k.y1; y++)
+    for (int x = k.x0; x < k.x1; x++) {
+      const float *centre = records.data() + (size_t) y * row + (size_t) x * FJ_TP_REC;
+      if (c.radius == 1) fj_tp_pixel_clamped<1>(k, B, c, centre, row, FJ_TP_REC, x, y);
+      else if (c.radius == 2) fj_tp_pixel_clamped<2>(k, B, c, centre, row, FJ_TP_REC, x, y);
+      else fj_tp_pixel_clamped<3>(k, B, c, centre, row, FJ_TP_REC, x, y);
+    }
   return 0;
+}
+
+// the arguments of fjgpu_denoise_temporal: the call above without a clamp
+int fj_denoise_temporal_host(const fjgpu_temporal_desc *d, const float *color, const float *position, const float *normal, const int32_t *ids,
+    const float *albedo, const float *variance_spatial, const fjgpu_view *prev_view, const float *prev_position, const float *prev_normal,
+    const int32_t *prev_ids, const fjgpu_temporal_history *prev, const fjgpu_temporal_history *next, float *variance_out)
+{
+  return fj_denoise_temporal_clamped_host(d, nullptr, color, position, normal, ids, albedo, variance_spatial, prev_view, prev_position, prev_normal,
+                                          prev_ids, prev, next, variance_out);
 }
 
 // sizeof of the structs the Python face mirrors, as the header's compiler lays them out
@@ -64,6 +95,7 @@ int fj_temporal_host_sizeof(const char *name)
   if (!strcmp(name, "fjgpu_view")) return (int) sizeof(fjgpu_view);
   if (!strcmp(name, "fjgpu_temporal_history")) return (int) sizeof(fjgpu_temporal_history);
   if (!strcmp(name, "fjgpu_temporal_desc")) return (int) sizeof(fjgpu_temporal_desc);
+  if (!strcmp(name, "fjgpu_temporal_clamp")) return (int) sizeof(fjgpu_temporal_clamp);
   return -1;
 }
 

@@ -115,6 +115,10 @@ class TemporalDesc(C.Structure):       # fjgpu_temporal_desc
     ]
 
 
+class TemporalClamp(C.Structure):      # fjgpu_temporal_clamp
+    _fields_ = [("radius", C.c_int32), ("gamma", C.c_float), ("stop_at_ids", C.c_int32), ("_pad", C.c_int32), ("amount", C.c_void_p)]
+
+
 class RenderStats(C.Structure):        # fj_render_stats
     _fields_ = [("render_seconds", C.c_double), ("prepare_seconds", C.c_double), ("rays", RayCounts)]
 

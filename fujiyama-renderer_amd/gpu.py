@@ -55,6 +55,8 @@ def lib():
                                              C.c_void_p, C.POINTER(ffi.View), C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(ffi.TemporalHistory), C.POINTER(ffi.TemporalHistory), C.c_void_p, C.c_void_p,
                                              C.POINTER(ffi.GpuStats)]
+        _tp = list(L.fjgpu_denoise_temporal.argtypes)          # the clamp goes behind the description
+        L.fjgpu_denoise_temporal_clamped.argtypes = _tp[:2] + [C.POINTER(ffi.TemporalClamp)] + _tp[2:]
         L.fjgpu_camera_samples.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_int, C.c_void_p, C.c_int]
         L.fjgpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.fjgpu_global_option.argtypes = [C.c_char_p, C.c_long]
@@ -629,6 +631,13 @@ MIN_HISTORY_VARIANCE = 4.0
 COS_NORMAL = 0.97
 TOL_POSITION_FRACTION = 0.05        # of the diagonal of the foreground's bounding box (TemporalDenoiser)
 
+# the clamp of temporal_accumulate(clamp=...) and TemporalDenoiser(clamp=...) that the grid of profiles/temporal_clamp.txt picks
+# (scripts/temporal_clamp_grid.py: the same pan, the cell with the smallest filtered error of the chain that is not demodulated: 0.186
+# against 0.249 unclamped -- and against 0.066 for the last frame filtered alone, which no cell reaches).  Neither call uses them unasked.
+CLAMP_RADIUS = 1
+CLAMP_GAMMA = 0.75
+CLAMP_STOP_AT_IDS = False
+
 HISTORY_NAMES = ("color", "moments", "length")
 HISTORY_CHANNELS = {"color": 4, "moments": 2, "length": 1}
 
@@ -654,10 +663,27 @@ def _history_struct(t):
     return h
 
 
+def _temporal_clamp(clamp):
+    """ffi.TemporalClamp (without an amount) of temporal_accumulate's `clamp`, or None"""
+    if clamp is None:
+        return None
+    if isinstance(clamp, dict):
+        unknown = sorted(set(clamp) - {"radius", "gamma", "stop_at_ids"})
+        if unknown or "radius" not in clamp or "gamma" not in clamp:
+            raise ValueError("clamp is a (radius, gamma) pair or a dict with radius, gamma and optionally stop_at_ids")
+        radius, gamma, stop = clamp["radius"], clamp["gamma"], clamp.get("stop_at_ids", CLAMP_STOP_AT_IDS)
+    else:
+        radius, gamma = clamp
+        stop = CLAMP_STOP_AT_IDS
+    cl = ffi.TemporalClamp()
+    cl.radius, cl.gamma, cl.stop_at_ids = int(radius), float(gamma), 1 if stop else 0
+    return cl
+
+
 def temporal_accumulate(color, position, normal, ids, albedo=None, variance_spatial=None, prev_view=None, prev_position=None,
                         prev_normal=None, prev_ids=None, prev=None, next=None, region=None, alpha_min=ALPHA_MIN, max_history=MAX_HISTORY,
                         tol_position=None, cos_normal=COS_NORMAL, min_history_variance=MIN_HISTORY_VARIANCE, albedo_floor=ALBEDO_FLOOR,
-                        device=0, stream=None, variance_out=None, to_host=True):
+                        device=0, stream=None, variance_out=None, to_host=True, clamp=None, clamp_amount=None):
     """Temporal accumulation of a beauty frame (include/fjgpu.h: fjgpu_denoise_temporal) -> (history, variance, GpuStats): history =
     {"color": [H, W, 4], "moments": [H, W, 2], "length": [H, W]}, variance [H, W], as numpy arrays -- or, with to_host=False, as the
     float32 tensors on the device the call wrote.  color [H, W, 4], position / normal [H, W, 3], ids [H, W, 4] int32 (Scene.render_aov's)
@@ -665,7 +691,10 @@ def temporal_accumulate(color, position, normal, ids, albedo=None, variance_spat
     camera), prev_position, prev_normal, prev_ids and prev (a history as returned) the previous one -- prev None: the first frame of a
     sequence.  numpy arrays are uploaded, device tensors used where they are.  next / variance_out: a history of contiguous float32
     device tensors / a tensor [H, W] to write instead of new ones (pixels outside the region are left as they are; new ones are 0
-    there); they must not be prev's or an input's.  tol_position is in world units (None, <= 0 or +inf: off), cos_normal <= -1: off."""
+    there); they must not be prev's or an input's.  tol_position is in world units (None, <= 0 or +inf: off), cos_normal <= -1: off.
+    clamp: None, or a (radius, gamma) pair or a dict with "radius", "gamma" and optionally "stop_at_ids" (default CLAMP_STOP_AT_IDS):
+    the history is clipped to the box of the current frame's window before the blend (fjgpu_denoise_temporal_clamped); clamp_amount: a
+    contiguous float32 device tensor [H, W] that receives how far each pixel's history was moved (it needs a clamp)."""
     import torch
     dev = torch.device("cuda", device)
     c = _device_tensor(color, "color", torch.float32, 4, dev)
@@ -692,6 +721,14 @@ def temporal_accumulate(color, position, normal, ids, albedo=None, variance_spat
     elif not (torch.is_tensor(variance_out) and variance_out.device == dev and variance_out.dtype == torch.float32 and
               variance_out.is_contiguous() and tuple(variance_out.shape) == hw):
         raise ValueError("variance_out must be a contiguous float32 tensor [H, W] on the device")
+    cl = _temporal_clamp(clamp)
+    if clamp_amount is not None:
+        if cl is None:
+            raise ValueError("clamp_amount needs a clamp")
+        if not (torch.is_tensor(clamp_amount) and clamp_amount.device == dev and clamp_amount.dtype == torch.float32 and
+                clamp_amount.is_contiguous() and tuple(clamp_amount.shape) == hw):
+            raise ValueError("clamp_amount must be a contiguous float32 tensor [H, W] on the device")
+        cl.amount = clamp_amount.data_ptr()
     d = ffi.TemporalDesc()
     d.yres, d.xres = hw
     d.region[:] = (0, 0, d.xres, d.yres) if region is None else tuple(int(v) for v in region)
@@ -703,9 +740,12 @@ def temporal_accumulate(color, position, normal, ids, albedo=None, variance_spat
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     h_prev = None if hp is None else C.byref(_history_struct(hp))
     h_next = _history_struct(hn)
-    _check(lib().fjgpu_denoise_temporal(device, C.byref(d), ptr(c), ptr(p), ptr(n), ptr(i), ptr(a), ptr(vs),
-                                        None if prev_view is None else C.byref(prev_view), ptr(pp), ptr(pn), ptr(pi), h_prev,
-                                        C.byref(h_next), ptr(variance_out), C.c_void_p(stream or 0), C.byref(st)))
+    args = (ptr(c), ptr(p), ptr(n), ptr(i), ptr(a), ptr(vs), None if prev_view is None else C.byref(prev_view), ptr(pp), ptr(pn), ptr(pi),
+            h_prev, C.byref(h_next), ptr(variance_out), C.c_void_p(stream or 0), C.byref(st))
+    if cl is None:
+        _check(lib().fjgpu_denoise_temporal(device, C.byref(d), *args))
+    else:
+        _check(lib().fjgpu_denoise_temporal_clamped(device, C.byref(d), C.byref(cl), *args))
     if to_host:
         return {k: t.cpu().numpy() for k, t in hn.items()}, variance_out.cpu().numpy(), st
     return hn, variance_out, st
@@ -723,19 +763,22 @@ class TemporalDenoiser(object):
     box of the first frame's foreground (a frame without foreground switches the terms off).  variance="samples": the beauty pass's sample
     variance (Scene.render_tiles(variance=...), the AOV call in front of it) is temporal_accumulate's variance_spatial -- the fallback for
     short histories -- and the spatial estimate is not run (info["estimate_stats"] is None); "spatial", the default, estimates it from
-    the frame.  The limits are the entry's: static scene,
+    the frame.  clamp: temporal_accumulate's -- None, the default, or e.g. (CLAMP_RADIUS, CLAMP_GAMMA): the history is clipped to the
+    current frame's neighbourhood before the blend.  The limits are the entry's: static scene,
     static camera per frame, fixed-grid sampler; frames from one and the same camera are identical and gain nothing."""
 
     _TEMPORAL = ("alpha_min", "max_history", "tol_position", "cos_normal", "min_history_variance")
     _FILTER = ("sigma_luminance", "iterations", "sigma_normal", "sigma_position", "stop_at_ids")
 
-    def __init__(self, scene, render, demodulate=True, stream=None, variance="spatial", **params):
+    def __init__(self, scene, render, demodulate=True, stream=None, variance="spatial", clamp=None, **params):
         for k in params:
             if k not in self._TEMPORAL + self._FILTER + ("albedo_floor",):
                 raise ValueError("unknown parameter %r" % k)
         if variance not in ("spatial", "samples"):
             raise ValueError("variance is \"spatial\" or \"samples\", not %r" % (variance,))
         self.variance = variance
+        _temporal_clamp(clamp)               # (refuses what temporal_accumulate would)
+        self.clamp = clamp
         self.scene, self.render_desc, self.demodulate, self.stream = scene, render.copy(), bool(demodulate), stream
         self.params = dict(params)
         self.albedo_floor = float(self.params.pop("albedo_floor", ALBEDO_FLOOR))
@@ -753,7 +796,7 @@ class TemporalDenoiser(object):
         (the scene's current camera).  info: "beauty_stats", "aov_stats", "estimate_stats", "temporal_stats", "denoise_stats" (GpuStats),
         "tol_position", "sigma_position" (the values used), "frame" (0 for the first of a sequence) and, with keep_inputs, "beauty",
         "aov", "variance_spatial" [H, W] (the temporal pass's fallback: the estimate, or the sample variance), "accumulated",
-        "history_length" [H, W] and "variance" [H, W] (the temporal pass's) as numpy copies."""
+        "history_length" [H, W] and "variance" [H, W] (the temporal pass's) and, with a clamp, "clamp_amount" [H, W] as numpy copies."""
         import torch
         sc, r = self.scene, self.render_desc
         dev = torch.device("cuda", sc._device)
@@ -795,11 +838,13 @@ class TemporalDenoiser(object):
                                                       fkw.get("sigma_normal", SIGMA_NORMAL), fkw["sigma_position"], fkw.get("stop_at_ids", True),
                                                       sc._device, self.stream)
         prev = self._prev
+        amount = torch.zeros((r.yres, r.xres), dtype=torch.float32, device=dev) if (self.clamp is not None and keep_inputs) else None
         hist, var_t, st_tmp = temporal_accumulate(
             fb, aov["position"], aov["normal"], aov["ids"], albedo=albedo, variance_spatial=var_s,
             prev_view=prev[0] if prev else None, prev_position=prev[1]["position"] if prev else None,
             prev_normal=prev[1]["normal"] if prev else None, prev_ids=prev[1]["ids"] if prev else None, prev=prev[2] if prev else None,
-            next=self._spare, region=region, albedo_floor=self.albedo_floor, device=sc._device, stream=self.stream, to_host=False, **tkw)
+            next=self._spare, region=region, albedo_floor=self.albedo_floor, device=sc._device, stream=self.stream, to_host=False,
+            clamp=self.clamp, clamp_amount=amount, **tkw)
         out = torch.zeros_like(fb)
         res, st_dn = denoise_variance(hist["color"], aov["normal"], aov["position"], aov["ids"], albedo=albedo, variance=var_t, region=region,
                                       device=sc._device, stream=self.stream, out=out, albedo_floor=self.albedo_floor, **fkw)
@@ -812,6 +857,8 @@ class TemporalDenoiser(object):
             info["accumulated"] = hist["color"].cpu().numpy()
             info["history_length"] = hist["length"].cpu().numpy()
             info["variance"] = var_t.cpu().numpy()
+            if amount is not None:
+                info["clamp_amount"] = amount.cpu().numpy()
         # ping-pong: what this frame read is what the next one writes
         self._spare = prev[2] if prev else None
         self._prev = (view, aov, hist)

@@ -432,6 +432,47 @@ int fjgpu_denoise_temporal(int device, const fjgpu_temporal_desc *desc,
     /* out            */ const fjgpu_temporal_history *next, float *variance_out /* [yres][xres] or NULL */,
     void *hip_stream, fjgpu_stats *stats);
 
+/* fjgpu_denoise_temporal with history rectification by variance clipping (Salvi, "An excursion in temporal supersampling", GDC 2016): between
+ * the fetch and the blend the fetched history is clipped to a box around the CURRENT frame's values in a window about the pixel.  Radiance that
+ * moves over a surface -- an emitter's rim under the pixel filter, highlights, reflections, shadows -- is invisible to ids, positions and
+ * normals, so its history is accepted and is wrong; the box is what the current frame says the pixel can plausibly be.  clamp NULL: this
+ * is fjgpu_denoise_temporal, bit for bit in every output.  The arithmetic is that pass's -- f32 without fused multiply-adds, sums left to
+ * right, csrc/device/fjgpu_temporal_math.h its one source (fj_tp_clamp; tests/temporal_clamp_model.py restates it) -- up to and
+ * including H /= valid weight.  A pixel without history is that pass's, and amount[p] = 0.  For a pixel p with history H_colour (4), (h1, h2):
+ *   window   taps q = p + (dx, dy), dy = -radius..radius outer, dx = -radius..radius inner.  A tap outside the region is skipped; with
+ *            stop_at_ids so is a tap with ids[q][0] != ids[p][0]; the centre always counts.  cnt = the sum of 1.f over the taps that count.
+ *   box      for each of five values X -- the four channels of the current colour C_q, and L_q, the luminance above computed for pixel q
+ *            (with q's albedo where there is one) --: pass 1  s1 += X_q, m = s1 / cnt;  pass 2, same taps  d = X_q - m, s2 += d * d,
+ *            sd = sqrtf(s2 / cnt);  lo = m - gamma * sd, hi = m + gamma * sd.
+ *   colour   H'_k = H_k < lo_k ? lo_k : (H_k > hi_k ? hi_k : H_k) for the four colour channels.
+ *   moments  h1' = h1 clipped likewise against the box of L; h2' = h2 where h1' == h1, else h2' = (h2 - h1 * h1) + h1' * h1': the history keeps
+ *            its spread around the moved mean.  The history length is untouched.
+ *   amount   amount[p] = the largest of |H'_k - H_k| over r, g, b (where amount is not NULL).
+ *   then     blend and variance of fjgpu_denoise_temporal from H', h1', h2'.
+ * Inputs must be finite.  A non-finite value of X among the taps that count makes that X's m, sd, lo and hi NaN; every comparison with
+ * them fails, so that value of the history passes unclipped (and amount counts nothing for it) on every pixel whose window holds the tap.
+ * Only region pixels of any buffer are read or written, amount included.  amount must not overlap any input, prev, next or variance_out.
+ * One kernel launch (k_tp_accumulate_clamped<radius>: the block's tile and halo of the current frame staged in LDS), no scratch, no
+ * atomics.  stats as fjgpu_denoise_temporal.
+ * Errors, all decided before any device call, every message starting "fjgpu_denoise_temporal_clamped:": those of fjgpu_denoise_temporal
+ * first and in its order; then, for a clamp that is not NULL, a radius outside 1..3; a gamma that is NaN, infinite or <= 0; an amount
+ * that overlaps another buffer.  FJGPU_ENODEV when no device is visible. */
+typedef struct fjgpu_temporal_clamp {
+  int32_t radius;        /* 1..3: the window is (2 radius + 1)^2 pixels of the CURRENT frame */
+  float   gamma;         /* finite, > 0: half-width of the box in standard deviations        */
+  int32_t stop_at_ids;   /* 1: a tap whose ids[q][0] differs from the centre's is skipped    */
+  int32_t _pad;
+  float  *amount;        /* DEVICE [yres][xres] f32 or NULL: how far the history was moved    */
+} fjgpu_temporal_clamp;
+
+int fjgpu_denoise_temporal_clamped(int device, const fjgpu_temporal_desc *desc, const fjgpu_temporal_clamp *clamp /* NULL: no clamp */,
+    /* current frame  */ const float *color, const float *position, const float *normal, const int32_t *ids,
+                         const float *albedo /* [3] or NULL */, const float *variance_spatial /* [yres][xres] or NULL */,
+    /* previous frame */ const fjgpu_view *prev_view, const float *prev_position, const float *prev_normal, const int32_t *prev_ids,
+                         const fjgpu_temporal_history *prev /* NULL: first frame */,
+    /* out            */ const fjgpu_temporal_history *next, float *variance_out /* [yres][xres] or NULL */,
+    void *hip_stream, fjgpu_stats *stats);
+
 /* Tunables (all have defaults): "batch_tiles" tiles per wavefront batch, "batch_samples" samples per batch where batch_tiles is 0
  * (0, the default: as many as the memory budget holds -- fastest where frames repeat; a caller that renders one frame per scene
  * sets a few M: the work arena shrinks from ~110 GB to a few GB at the headline size and the cold frame starts sooner),
