@@ -28,6 +28,7 @@
 #include "fjgpu_lbvh.h"
 #include "fjgpu_light_cone.h"
 #include "fjgpu_light_hull.h"
+#include "fjgpu_matte.h"
 #include "fjgpu_raysort.h"
 #include "fjgpu_sample_variance.h"
 #include "fjgpu_tlas.h"
@@ -2434,13 +2435,15 @@ static TileDesc aov_tile(const fj_render_desc *r, const fjgpu::TileRect &t, cons
 }
 
 // the body of fjgpu_render_aov and fjgpu_render_aov_albedo: one camera-ray generation and one closest-hit walk per batch, then k_aov_reduce
-// where a member of `out` is set, then k_aov_albedo where d_albedo is set.  `who` is the entry point's name in the messages.
+// where a member of `out` is set, then k_aov_albedo where d_albedo is set, then k_aov_matte (fjgpu_matte.hip) where `matte` is set
+// (fjgpu_render_aov_matte: its description and buffers, checked by the caller).  `who` is the entry point's name in the messages.
+struct MatteCall { const fjgpu_matte_desc *desc; const fjgpu_matte_buffers *out; };
 static int render_aov_body(const char *who_, fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
-    const fjgpu_aov_buffers *out, float *d_albedo, void *hip_stream, fjgpu_stats *stats)
+    const fjgpu_aov_buffers *out, float *d_albedo, void *hip_stream, fjgpu_stats *stats, const MatteCall *matte = nullptr)
 {
   const std::string who(who_);
   const bool reduce = out && (out->depth || out->position || out->normal || out->uv || out->ids || out->coverage);
-  if (!reduce && !d_albedo) return fail(FJGPU_EINVAL, who + ": every buffer pointer is NULL, nothing to write");
+  if (!reduce && !d_albedo && !matte) return fail(FJGPU_EINVAL, who + ": every buffer pointer is NULL, nothing to write");
   if (tile_ids && n_tiles < 0) return fail(FJGPU_EINVAL, who + ": negative tile count");
   AovSetup A;
   if (const int e = aov_setup(sc, r, who_, &A)) return e;
@@ -2502,6 +2505,18 @@ static int render_aov_body(const char *who_, fjgpu_scene *sc, const fj_render_de
   bp.lanes = 1; bp.lanes_log2 = 0;      // lanes per pixel: the smallest power of two >= min(samples per pixel, 64)
   while (bp.lanes < 64 && (long) bp.lanes < (long) r->rate_x * r->rate_y) { bp.lanes <<= 1; bp.lanes_log2++; }
   bp.albedo = d_albedo;
+  ResolveParams mrp;       // the frame and the filter window as the beauty pass's resolve sees them
+  MatteParams mp;
+  std::memset(&mrp, 0, sizeof(mrp));
+  std::memset(&mp, 0, sizeof(mp));
+  if (matte) {
+    mrp.xres = r->xres; mrp.yres = r->yres; mrp.rate_x = r->rate_x; mrp.rate_y = r->rate_y;
+    mrp.npx_x = r->rate_x + 2 * A.margin[0]; mrp.npx_y = r->rate_y + 2 * A.margin[1];
+    mrp.fw = (double) r->filter_w; mrp.fh = (double) r->filter_h;
+    mp.key = matte->desc->key; mp.ranks = matte->desc->ranks; mp.filtered = matte->desc->filtered ? 1 : 0;
+    mp.margin_x = A.margin[0]; mp.margin_y = A.margin[1];
+    mp.ids = matte->out->ids; mp.coverage = matte->out->coverage; mp.rest = matte->out->rest; mp.distinct = matte->out->distinct;
+  }
 
   // event pairs around every launch, turned into durations after the one synchronisation at the end
   struct Span { hipEvent_t a, b; double *bucket; };
@@ -2534,6 +2549,8 @@ static int render_aov_body(const char *who_, fjgpu_scene *sc, const fj_render_de
     if (reduce) rc = timed(&acc.resolve_ms, [&]() { return launch_aov_reduce(st, S, ap, tiles, B.n, B.max_px, d_rays, d_hits); });
     if (rc) break;
     if (d_albedo) rc = timed(&acc.resolve_ms, [&]() { return launch_aov_albedo(st, S, bp, tiles, B.n, B.max_px, d_hits); });
+    if (rc) break;
+    if (matte) rc = timed(&acc.resolve_ms, [&]() { return launch_aov_matte(st, S.instances, mrp, mp, tiles, B.n, B.max_px, d_suv, d_hits); });
     if (rc) break;
     acc.rays.camera += B.samples;
     acc.trace_launches++; acc.closest_launches++; acc.batches++;
@@ -2570,6 +2587,21 @@ int fjgpu_render_aov_albedo(fjgpu_scene *sc, const fj_render_desc *r, const int3
 {
   if (!sc || !r) return fail(FJGPU_EINVAL, "fjgpu_render_aov_albedo: null argument (scene and render are required)");
   return render_aov_body("fjgpu_render_aov_albedo", sc, r, tile_ids, n_tiles, out, d_albedo, hip_stream, stats);
+}
+
+int fjgpu_render_aov_matte(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
+    const fjgpu_matte_desc *matte, const fjgpu_matte_buffers *out, void *hip_stream, fjgpu_stats *stats)
+{
+  if (!sc || !r) return fail(FJGPU_EINVAL, "fjgpu_render_aov_matte: null argument (scene and render are required)");
+  if (!matte) return fail(FJGPU_EINVAL, "fjgpu_render_aov_matte: null matte description");
+  if (!out) return fail(FJGPU_EINVAL, "fjgpu_render_aov_matte: null buffer struct");
+  if (!out->ids || !out->coverage) return fail(FJGPU_EINVAL, "fjgpu_render_aov_matte: the ids and coverage buffers are required (NULL pointer)");
+  if (matte->key != FJGPU_MATTE_KEY_INSTANCE && matte->key != FJGPU_MATTE_KEY_SHADER)
+    return fail(FJGPU_EINVAL, "fjgpu_render_aov_matte: unknown key " + std::to_string(matte->key) + " (FJGPU_MATTE_KEY_INSTANCE or FJGPU_MATTE_KEY_SHADER)");
+  if (matte->ranks < 1 || matte->ranks > FJGPU_MATTE_MAX_RANKS)
+    return fail(FJGPU_EINVAL, "fjgpu_render_aov_matte: ranks " + std::to_string(matte->ranks) + " outside 1.." + std::to_string(FJGPU_MATTE_MAX_RANKS));
+  const MatteCall mc{matte, out};
+  return render_aov_body("fjgpu_render_aov_matte", sc, r, tile_ids, n_tiles, nullptr, nullptr, hip_stream, stats, &mc);
 }
 
 int fjgpu_camera_samples(fjgpu_scene *sc, const fj_render_desc *r, int tile_id, double *rays8, int cap)

@@ -58,6 +58,21 @@ class AovBuffers(C.Structure):         # fjgpu_aov_buffers: DEVICE pointers, 0 =
     _fields_ = [(n, C.c_void_p) for n in ("depth", "position", "normal", "uv", "ids", "coverage")]
 
 
+class MatteDesc(C.Structure):          # fjgpu_matte_desc
+    _fields_ = [("key", C.c_int32), ("ranks", C.c_int32), ("filtered", C.c_int32), ("_pad", C.c_int32)]
+
+
+class MatteBuffers(C.Structure):       # fjgpu_matte_buffers: DEVICE pointers; rest and distinct: 0 = not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("ids", "coverage", "rest", "distinct")]
+
+
+MATTE_KEYS = {"instance": 0, "shader": 1}      # FJGPU_MATTE_KEY_*
+MATTE_MAX_RANKS = 16                           # FJGPU_MATTE_MAX_RANKS
+
+# fjgpu_render_aov_matte: scene, render, tile_ids, n_tiles, matte, buffers, hip_stream, stats
+RENDER_AOV_MATTE_ARGTYPES = [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_int, C.POINTER(MatteDesc), C.POINTER(MatteBuffers), C.c_void_p,
+                             C.POINTER(GpuStats)]
+
 # fjgpu_render_tiles_variance: scene, render, tile_ids, n_tiles, d_framebuffer, d_albedo, albedo_floor, d_variance, hip_stream, stats
 RENDER_TILES_VARIANCE_ARGTYPES = [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                   C.c_void_p, C.POINTER(GpuStats)]

@@ -38,6 +38,7 @@ def lib():
                                        C.c_void_p, C.POINTER(ffi.GpuStats)]
         L.fjgpu_render_aov_albedo.argtypes = [C.c_void_p, C.POINTER(ffi.RenderDesc), C.c_void_p, C.c_int, C.POINTER(ffi.AovBuffers),
                                               C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
+        L.fjgpu_render_aov_matte.argtypes = ffi.RENDER_AOV_MATTE_ARGTYPES
         L.fjgpu_denoise_albedo.argtypes = [C.c_int, C.POINTER(ffi.DenoiseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_float, C.c_void_p, C.c_void_p, C.POINTER(ffi.GpuStats)]
         L.fjgpu_denoise.argtypes = [C.c_int, C.POINTER(ffi.DenoiseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -82,6 +83,28 @@ def device_count():
 AOV_NAMES = ("depth", "position", "normal", "uv", "ids", "coverage")       # the members of fjgpu_aov_buffers
 AOV_ALL = AOV_NAMES + ("albedo",)                                           # ... and the buffer of fjgpu_render_aov_albedo (Scene.render_aov_albedo)
 AOV_CHANNELS = {"depth": 1, "position": 3, "normal": 3, "uv": 2, "ids": 4, "coverage": 1, "albedo": 3}
+
+
+MATTE_NAMES = ("ids", "coverage", "rest", "distinct")                      # the members of fjgpu_matte_buffers
+
+
+def matte_select(ids, coverage, keys):
+    """One matte out of the ranked ones (Scene.render_matte / Scene._render_matte_device): ids, coverage [H, W, ranks] (numpy arrays or
+    torch tensors) and the keys that make up the object -> [H, W] float32 of the same kind: per pixel the sum, rank by rank, of the
+    coverage of the ranks whose id is in `keys`.  Plumbing, no kernel."""
+    keys = [int(k) for k in np.atleast_1d(keys)]
+    if isinstance(ids, np.ndarray):
+        sel = np.isin(ids, np.asarray(keys, dtype=ids.dtype))
+        out = np.zeros(ids.shape[:2], dtype=np.float32)
+        for r in range(ids.shape[2]):
+            out += np.where(sel[:, :, r], coverage[:, :, r], np.float32(0))
+        return out
+    import torch
+    sel = torch.isin(ids, torch.tensor(keys, dtype=ids.dtype, device=ids.device))
+    out = torch.zeros(ids.shape[:2], dtype=torch.float32, device=ids.device)
+    for r in range(ids.shape[2]):
+        out += torch.where(sel[:, :, r], coverage[:, :, r], torch.zeros((), dtype=torch.float32, device=ids.device))
+    return out
 
 
 class Scene(object):
@@ -214,6 +237,44 @@ class Scene(object):
                                                  C.c_void_p(stream or 0), C.byref(st)))
         else:
             _check(lib().fjgpu_render_aov(self._h, C.byref(render), ids_p, n, C.byref(bufs), C.c_void_p(stream or 0), C.byref(st)))
+        return tensors, st
+
+    def render_matte(self, render, key="instance", ranks=4, filtered=True, tile_ids=None, prefill=None, stream=None):
+        """Ranked id/coverage mattes (include/fjgpu.h: fjgpu_render_aov_matte) of the listed tiles (None = all tiles of the render
+        region): per pixel the `ranks` keys with the greatest share of the pixel and those shares.  key: "instance" or "shader" (or the
+        number of a FJGPU_MATTE_KEY_*); filtered: the shares of the beauty pixel's filter window under its weights (True) or of the
+        pixel's own samples (False).  -> ({"ids": [H, W, ranks] int32 (-1: empty rank), "coverage": [H, W, ranks] f32, "rest": [H, W, 1]
+        f32 (the share of the hit keys that did not fit), "distinct": [H, W, 1] int32}, GpuStats), numpy arrays; `prefill` as in
+        render_aov.  matte_select() turns a set of keys into one matte."""
+        tensors, st = self._render_matte_device(render, key, ranks, filtered, tile_ids, prefill, stream)
+        return {name: t.cpu().numpy() for name, t in tensors.items()}, st
+
+    def _render_matte_device(self, render, key="instance", ranks=4, filtered=True, tile_ids=None, prefill=None, stream=None):
+        """render_matte with the buffers left where the pass wrote them -> ({name: torch tensor on the scene's device}, GpuStats)"""
+        import torch
+        if isinstance(key, str):
+            if key not in ffi.MATTE_KEYS:
+                raise ValueError("unknown matte key %r (one of %s)" % (key, ", ".join(sorted(ffi.MATTE_KEYS))))
+            key = ffi.MATTE_KEYS[key]
+        desc = ffi.MatteDesc(int(key), int(ranks), 1 if filtered else 0, 0)
+        dev = torch.device("cuda", self._device)
+        k = max(1, min(int(ranks), ffi.MATTE_MAX_RANKS))      # (a refused rank count still gets buffers: the refusal is the library's)
+        bufs = ffi.MatteBuffers()
+        tensors = {}
+        for name in MATTE_NAMES:
+            dtype = torch.float32 if name in ("coverage", "rest") else torch.int32
+            fill = prefill.get(name, 0) if isinstance(prefill, dict) else (0 if prefill is None else prefill)
+            tensors[name] = torch.full((render.yres, render.xres, k if name in ("ids", "coverage") else 1), fill, dtype=dtype, device=dev)
+            setattr(bufs, name, tensors[name].data_ptr())
+        torch.cuda.synchronize(dev)          # the fills ran on torch's stream
+        st = ffi.GpuStats()
+        if tile_ids is None:
+            ids_p, n = None, 0
+        else:
+            ids = np.ascontiguousarray(tile_ids, dtype=np.int32)
+            ids_p, n = ids.ctypes.data_as(C.c_void_p), len(ids)
+        _check(lib().fjgpu_render_aov_matte(self._h, C.byref(render), ids_p, n, C.byref(desc), C.byref(bufs), C.c_void_p(stream or 0),
+                                            C.byref(st)))
         return tensors, st
 
     def render_denoised(self, render, keep_inputs=False, stream=None, demodulate=False, variance_guided=False, variance="spatial", **kw):

@@ -235,6 +235,41 @@ int fjgpu_render_aov_albedo(fjgpu_scene *scene, const fj_render_desc *render, co
     const fjgpu_aov_buffers *buffers /* may be NULL */, float *d_albedo /* DEVICE [yres][xres][3], may be NULL */,
     void *hip_stream, fjgpu_stats *stats);
 
+/* Ranked id/coverage mattes (Cryptomatte-style): per pixel the `ranks` keys with the greatest share of the pixel and those shares, so
+ * that a compositor can isolate an object at the beauty frame's anti-aliased edges.  The AOV pass's camera rays and closest-hit walk,
+ * then one reduction over the hit records.  For a pixel p, samples s with a key k_s and a weight w_s:
+ *   filtered = 1   the samples of the filter window the beauty pass resolves p from, w_s = its Gaussian weight in f64
+ *                  (exp(-2 (xx xx + yy yy)), xx = 2 (xres u - (px + .5)) / filter_w, yy likewise from yres (1 - v)): the shares are
+ *                  those of the beauty pixel's blend
+ *   filtered = 0   the pixel's own rate_x * rate_y samples (fjgpu_render_aov's), w_s = 1
+ *   k_s            -1 for a miss; key FJGPU_MATTE_KEY_INSTANCE: the hit's instance (ids[0] of the ids AOV); FJGPU_MATTE_KEY_SHADER: the
+ *                  shader index by the slot rule above (ids[3]) of the sample's own shading group -- a hit whose shader is unassigned
+ *                  has key -1 as well.  A key of -1 is never ranked; its weight counts in W only.
+ *   W = sum of w_s over all samples.  Keys are visited in ascending order; A(key) = sum of w_s with that key (f64); (key, A) is inserted
+ *   into a list of `ranks` entries before the first entry whose weight is strictly smaller, so equal weights stay in ascending key
+ *   order; what leaves the list (or never enters a full one) adds its weight to R.
+ *   ids[r], coverage[r] = (float) (A_r / W) rank by rank, -1 and 0 for an empty rank; rest = (float) (R / W), the share of hit keys that
+ *   did not fit into `ranks`; distinct = the number of keys visited.  sum(coverage) + rest is the pixel's hit share (filtered: the alpha of
+ *   an opaque scene's beauty pixel).  With filtered = 0 every sum is a count and the quotients are (float) count / (float) samples, the
+ *   statement of fjgpu_render_aov's coverage.
+ * Limits: those of fjgpu_render_aov (static scene and camera, fixed-grid sampler, one device); first hits only -- the matte of a glass
+ * object is the glass, not what is seen through it.
+ * Everything else is fjgpu_render_aov's: tiles, region, untouched pixels, batches ("aov_batch_samples"), transient buffers, stats
+ * (resolve_ms is the matte reduction) and the refusals, the messages naming fjgpu_render_aov_matte.  FJGPU_EINVAL, with the reason, for
+ * a NULL description or buffer struct, a NULL ids or coverage buffer, an unknown key and ranks outside 1..FJGPU_MATTE_MAX_RANKS. */
+#define FJGPU_MATTE_KEY_INSTANCE 0   /* ids[0] of the ids AOV */
+#define FJGPU_MATTE_KEY_SHADER   1   /* ids[3]: ObjectInstance::GetShader of the sample's shading group */
+#define FJGPU_MATTE_MAX_RANKS    16
+typedef struct fjgpu_matte_desc { int32_t key, ranks, filtered, pad; } fjgpu_matte_desc;
+typedef struct fjgpu_matte_buffers {      /* DEVICE pointers, row-major */
+  int32_t *ids;        /* [yres*xres*ranks]  key of rank r, -1 = empty rank     (required) */
+  float   *coverage;   /* [yres*xres*ranks]  its share of the pixel, 0 if empty (required) */
+  float   *rest;       /* [yres*xres]  share of hit keys that did not fit into `ranks` (optional) */
+  int32_t *distinct;   /* [yres*xres]  number of distinct keys among the pixel's samples (optional) */
+} fjgpu_matte_buffers;
+int fjgpu_render_aov_matte(fjgpu_scene *scene, const fj_render_desc *render, const int32_t *tile_ids, int n_tiles,
+    const fjgpu_matte_desc *matte, const fjgpu_matte_buffers *buffers, void *hip_stream, fjgpu_stats *stats);
+
 /* Diagnostics: the camera rays of one tile exactly as fjgpu_render_aov (and the beauty pass) traces them, HOST arrays:
  * rays8 [n][8] = orig xyz, dir xyz, znear, zfar in sample order k = y * nx + x (margin samples included) -- the layout
  * fjgpu_trace takes.  Writes at most `cap` rays (cap 0: none, rays8 may be NULL); returns the tile's sample count n, or a
