@@ -196,6 +196,9 @@ struct fjgpu_scene {
   TileDesc *d_tiles;
   double *d_jit, *d_tim;
   size_t tab_len;
+  long sampler_seed = 0;           // option "sampler_seed" (0..65535, default 0: the streams of the reference): the jitter / time tables are those of
+                                   // XorShiftTableSeeded and TileDesc.id is SeededTileId of it, in every entry that draws ("Random streams")
+  long tab_seed = 0;               // the seed d_jit / d_tim were built with
   int tiles_cap;
   int stack_need;
   double tri_record_bytes;         // 36 when every mesh is stored as f32 triangles, else 72
@@ -1223,6 +1226,7 @@ int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value)
   if (n == "scene_bytes") { *value = (double) scene->mem.bytes; return 0; }
   if (n == "work_bytes") { *value = (double) (scene->work ? scene->work->bytes : 0); return 0; }
   if (n == "stack_need") { *value = scene->stack_need; return 0; }
+  if (n == "sampler_seed") { *value = (double) scene->sampler_seed; return 0; }
   if (n == "blas_nodes") { *value = (double) scene->blas_nodes; return 0; }
   if (n == "blas_treelet_passes") { *value = (double) scene->blas_treelet_passes; return 0; }
   if (n == "blas_treelets_changed") { *value = (double) scene->blas_treelets_changed; return 0; }
@@ -1417,6 +1421,11 @@ int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value)
   if (n == "count_all_shadow") { scene->count_all_shadow = value != 0; return 0; }
   if (n == "light_cones") { scene->light_cones = value != 0; return 0; }
   if (n == "light_hulls") { scene->light_hulls = value != 0; return 0; }
+  if (n == "sampler_seed") {
+    if (value < 0 || value > 65535) return fail(FJGPU_EINVAL, "sampler_seed: " + std::to_string(value) + " is outside 0..65535 (0: the unseeded streams)");
+    scene->sampler_seed = value;      // (the tables follow at the next call that reads them: ensure_work)
+    return 0;
+  }
   if (n == "overlap_shadow") {
     if (value < 0 || value > 2) return fail(FJGPU_EINVAL, "overlap_shadow: 0 off, 1 on, 2 by the batch size");
     scene->overlap = value;
@@ -1514,10 +1523,18 @@ int ensure_work(fjgpu_scene *sc, size_t samples, size_t rays, int tiles, size_t 
   if (tab_len > sc->tab_len) {
     // the tables live with the scene (small): 3 draws per sample of the largest tile
     std::vector<double> draws;
-    fjgpu::XorShiftTable(2 * tab_len, &draws);
+    fjgpu::XorShiftTableSeeded((unsigned) sc->sampler_seed, 2 * tab_len, &draws);
     if (sc->mem.upload(draws.data(), 2 * tab_len, const_cast<const double **>(&sc->d_jit))) return -1;
     if (sc->mem.upload(draws.data(), tab_len, const_cast<const double **>(&sc->d_tim))) return -1;
     sc->tab_len = tab_len;
+    sc->tab_seed = sc->sampler_seed;
+  } else if (sc->tab_seed != sc->sampler_seed) {
+    // another seed, the same length: the draws go into the tables that are there (no call is in flight: every render call ends synchronised)
+    std::vector<double> draws;
+    fjgpu::XorShiftTableSeeded((unsigned) sc->sampler_seed, 2 * sc->tab_len, &draws);
+    if (hipMemcpy(sc->d_jit, draws.data(), sizeof(double) * 2 * sc->tab_len, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (hipMemcpy(sc->d_tim, draws.data(), sizeof(double) * sc->tab_len, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    sc->tab_seed = sc->sampler_seed;
   }
   return 0;
 }
@@ -1859,7 +1876,7 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
     for (int k = 0; k < nb; k++) {
       const fjgpu::TileRect &t = all[ids[b0 + k]];
       TileDesc &d = td[k];
-      d.xmin = t.xmin; d.ymin = t.ymin; d.xmax = t.xmax; d.ymax = t.ymax; d.id = t.id;
+      d.xmin = t.xmin; d.ymin = t.ymin; d.xmax = t.xmax; d.ymax = t.ymax; d.id = fjgpu::SeededTileId(t.id, (unsigned) sc->sampler_seed);
       d.nx = r->rate_x * (t.xmax - t.xmin) + 2 * margin[0];
       d.ny = r->rate_y * (t.ymax - t.ymin) + 2 * margin[1];
       d.cell_offset = cell_off; d.pad = 0;
@@ -2424,10 +2441,10 @@ static int aov_setup(fjgpu_scene *sc, const fj_render_desc *r, const char *who, 
   a->S.shadow_join = nullptr;
   return 0;
 }
-static TileDesc aov_tile(const fj_render_desc *r, const fjgpu::TileRect &t, const int *margin, uint32_t sample_offset)
+static TileDesc aov_tile(const fjgpu_scene *sc, const fj_render_desc *r, const fjgpu::TileRect &t, const int *margin, uint32_t sample_offset)
 {
   TileDesc d;
-  d.xmin = t.xmin; d.ymin = t.ymin; d.xmax = t.xmax; d.ymax = t.ymax; d.id = t.id;
+  d.xmin = t.xmin; d.ymin = t.ymin; d.xmax = t.xmax; d.ymax = t.ymax; d.id = fjgpu::SeededTileId(t.id, (unsigned) sc->sampler_seed);
   d.nx = r->rate_x * (t.xmax - t.xmin) + 2 * margin[0];
   d.ny = r->rate_y * (t.ymax - t.ymin) + 2 * margin[1];
   d.sample_offset = sample_offset; d.cell_offset = 0; d.pad = 0;
@@ -2466,7 +2483,7 @@ static int render_aov_body(const char *who_, fjgpu_scene *sc, const fj_render_de
   size_t cap_samples = 0, tab_len = 0;
   for (size_t k = 0; k < ids.size(); k++) {
     const fjgpu::TileRect &t = A.all[ids[k]];
-    TileDesc d = aov_tile(r, t, A.margin, 0);
+    TileDesc d = aov_tile(sc, r, t, A.margin, 0);
     const size_t ts = (size_t) d.nx * (size_t) d.ny;
     if (ts > 0x7fffffffu) return fail(FJGPU_EINVAL, who + ": a tile of more than 2^31 samples: lower the tilesize");
     if (batches.empty() || batches.back().n >= 65535 || (size_t) batches.back().samples + ts > limit) batches.push_back(Batch{k, 0, 0u, 0u, 0});
@@ -2489,7 +2506,7 @@ static int render_aov_body(const char *who_, fjgpu_scene *sc, const fj_render_de
   {
     // the per-tile XorShift stream as a table (draw k is the same number in every tile): two draws per sample of the largest tile
     std::vector<double> draws;
-    fjgpu::XorShiftTable(2 * tab_len, &draws);
+    fjgpu::XorShiftTableSeeded((unsigned) sc->sampler_seed, 2 * tab_len, &draws);
     if (W.upload(draws.data(), 2 * tab_len, &d_jit)) return fail(FJGPU_ENOMEM, who + ": device allocation failed");
   }
   HIP_TRY(hipMemcpy(d_tiles, td.data(), sizeof(TileDesc) * td.size(), hipMemcpyHostToDevice));
@@ -2610,7 +2627,7 @@ int fjgpu_camera_samples(fjgpu_scene *sc, const fj_render_desc *r, int tile_id, 
   AovSetup A;
   if (const int e = aov_setup(sc, r, "fjgpu_camera_samples", &A)) return e;
   if (tile_id < 0 || tile_id >= (int) A.all.size()) return fail(FJGPU_EINVAL, "tile id out of range");
-  const TileDesc d = aov_tile(r, A.all[tile_id], A.margin, 0);
+  const TileDesc d = aov_tile(sc, r, A.all[tile_id], A.margin, 0);
   const size_t n = (size_t) d.nx * (size_t) d.ny;
   if (n > 0x7fffffffu) return fail(FJGPU_EINVAL, "fjgpu_camera_samples: a tile of more than 2^31 samples");
   if (cap == 0) return (int) n;
@@ -2619,7 +2636,7 @@ int fjgpu_camera_samples(fjgpu_scene *sc, const fj_render_desc *r, int tile_id, 
   double *d_suv; DRay *d_rays; DPath *d_paths;
   const double *d_jit = nullptr; const TileDesc *d_tile = nullptr;
   std::vector<double> draws;
-  fjgpu::XorShiftTable(2 * n, &draws);
+  fjgpu::XorShiftTableSeeded((unsigned) sc->sampler_seed, 2 * n, &draws);
   if (W.alloc(n * 2, &d_suv) || W.alloc(n, &d_rays) || W.alloc(n, &d_paths) || W.upload(draws.data(), 2 * n, &d_jit) || W.upload(&d, 1, &d_tile))
     return fail(FJGPU_ENOMEM, "fjgpu_camera_samples: device allocation failed");
   DScene S = A.S;

@@ -96,6 +96,12 @@ void GenerateTiles(const fj_render_desc &r, std::vector<TileRect> *tiles);
 void SamplerMargin(const fj_render_desc &r, int margin[2]);
 // first n draws of the default-seeded XorShift as f64 in [0,1]
 void XorShiftTable(size_t n, std::vector<double> *out);
+// the same of the sampler seed `seed` (option "sampler_seed"): 0 is the table above, s != 0 the draws of the reference's seeded generator,
+// XorShift(unsigned seed) of src/fj_random.cc:18-24 with seed = s
+void XorShiftTableSeeded(unsigned seed, size_t n, std::vector<double> *out);
+// what the host writes into TileDesc.id under the sampler seed: id + 4096 seed, which sample_uid (fjgpu_dev_shade.h) folds to uid ^ seed * 0x9E3779B1
+// for a tile id below 4096 ("Random streams"); seed 0: id
+inline int SeededTileId(int id, unsigned seed) { return (int) ((unsigned) id + 4096u * seed); }
 double CameraUvSizeY(double fov);
 
 }  // namespace fjgpu

@@ -1,6 +1,6 @@
 // fjgpu_image_api.hip -- C ABI of libfjgpu.so (include/fjgpu.h), the image-space passes: entry points that take a device index,
 // frame-sized DEVICE buffers and a small description, and no fjgpu_scene.  Each one is its refusals, its transient buffers and a handful
-// of launches (fjgpu_denoise.hip, fjgpu_denoise_variance.hip, fjgpu_temporal.hip) inside one shared call frame, ImageCall.
+// of launches (fjgpu_denoise.hip, fjgpu_denoise_variance.hip, fjgpu_temporal.hip, fjgpu_accumulate.hip) inside one shared call frame, ImageCall.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -9,6 +9,7 @@
 #include <string>
 
 #include "fjgpu.h"
+#include "fjgpu_accumulate.h"
 #include "fjgpu_api_common.h"
 #include "fjgpu_denoise.h"
 #include "fjgpu_denoise_variance.h"
@@ -149,6 +150,26 @@ bool tp_overlap(const void *a, size_t na, const void *b, size_t nb)
   if (!a || !b) return false;
   const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
   return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// ---- the rectangle list of the accumulation's two entries: n_rects >= 0 rectangles inside the frame, none empty (rects NULL: the whole
+// frame, n_rects is not read).  *list: the rectangles to upload; *max_patches: the 16 x 16 patches of the largest.
+int ac_check_rects(const std::string &f, int xres, int yres, const int32_t *rects, int n_rects, std::vector<int32_t> *list, uint32_t *max_patches)
+{
+  if (xres <= 0 || yres <= 0) return fail(FJGPU_EINVAL, f + ": resolution must be positive");
+  if (rects && n_rects < 0) return fail(FJGPU_EINVAL, f + ": n_rects is negative");
+  if (rects) list->assign(rects, rects + 4 * (size_t) n_rects);
+  else *list = {0, 0, xres, yres};
+  *max_patches = 0;
+  for (size_t i = 0; i < list->size(); i += 4) {
+    const int32_t *r = list->data() + i;
+    if (r[0] < 0 || r[1] < 0 || r[2] > xres || r[3] > yres || r[0] >= r[2] || r[1] >= r[3])
+      return fail(FJGPU_EINVAL, f + ": rect " + std::to_string(i / 4) + " must be a non-empty rectangle inside the frame");
+    const unsigned long long n = (unsigned long long) ((r[2] - r[0] + FJ_AC_BX - 1) / FJ_AC_BX) * (unsigned long long) ((r[3] - r[1] + FJ_AC_BY - 1) / FJ_AC_BY);
+    if (n > 0x7fffffffull) return fail(FJGPU_EINVAL, f + ": a rect of more than 2^31 - 1 patches of 16 x 16 pixels");
+    *max_patches = std::max(*max_patches, (uint32_t) n);
+  }
+  return 0;
 }
 
 }  // namespace
@@ -401,6 +422,82 @@ int fjgpu_denoise_temporal_clamped(int device, const fjgpu_temporal_desc *d, con
 {
   return temporal("fjgpu_denoise_temporal_clamped", device, d, clamp, color, position, normal, ids, albedo, variance_spatial, prev_view,
                   prev_position, prev_normal, prev_ids, prev, next, variance_out, hip_stream, stats);
+}
+
+// ---- progressive accumulation (fjgpu_accumulate.hip, fjgpu_accum_math.h).  One launch each; the only transient buffers are the rectangle
+// list and, for the errors, one float per rectangle.  Every refusal is decided before a device call.
+int fjgpu_accumulate(int device, int xres, int yres, const int32_t *rects, int n_rects, const float *color, const fjgpu_accum_state *state,
+    int reset, float *variance_out, void *hip_stream, fjgpu_stats *stats)
+{
+  ImageCall call("fjgpu_accumulate", hip_stream);
+  const std::string &f = call.f;
+  if (!color || !state || !state->mean || !state->m2 || !state->count)
+    return fail(FJGPU_EINVAL, f + ": null argument (color, state and its mean, m2 and count are required)");
+  std::vector<int32_t> list;
+  uint32_t max_patches = 0;
+  if (const int e = ac_check_rects(f, xres, yres, rects, n_rects, &list, &max_patches)) return e;
+  {
+    const size_t px = (size_t) xres * (size_t) yres * sizeof(float);
+    const struct { const void *p; size_t n; } planes[3] = {{state->mean, 4 * px}, {state->m2, px}, {state->count, px}};
+    for (int a = 0; a < 3; a++)
+      if (tp_overlap(color, 4 * px, planes[a].p, planes[a].n)) return fail(FJGPU_EINVAL, f + ": color overlaps a plane of the state");
+    for (int a = 0; a < 3; a++)
+      if (tp_overlap(variance_out, px, planes[a].p, planes[a].n)) return fail(FJGPU_EINVAL, f + ": variance_out overlaps a plane of the state");
+    for (int a = 0; a < 3; a++)
+      for (int b = a + 1; b < 3; b++)
+        if (tp_overlap(planes[a].p, planes[a].n, planes[b].p, planes[b].n)) return fail(FJGPU_EINVAL, f + ": the planes of the state overlap each other");
+    if (tp_overlap(variance_out, px, color, 4 * px)) return fail(FJGPU_EINVAL, f + ": variance_out overlaps color");
+  }
+  if (((uintptr_t) color | (uintptr_t) state->mean) & 15u) return fail(FJGPU_EINVAL, f + ": color and the state's mean must be 16-byte aligned");
+  const int n = (int) (list.size() / 4);
+  if ((unsigned long long) n * max_patches > 0x7fffffffull) return fail(FJGPU_EINVAL, f + ": more than 2^31 - 1 blocks (rects times the patches of the largest): split the list");
+  if (const int e = call.open(device)) return e;
+  fjgpu_stats none;
+  std::memset(&none, 0, sizeof(none));
+  if (n == 0) { if (stats) *stats = none; return 0; }
+  DeviceBuffers W;
+  const int32_t *d_rects = nullptr;
+  if (W.upload(list.data(), list.size(), &d_rects)) return fail(FJGPU_ENOMEM, f + ": device allocation failed");
+  AcBuffers B;
+  B.color = color; B.mean = state->mean; B.m2 = state->m2; B.count = state->count; B.variance_out = variance_out;
+  call.start(2);
+  if (!call.rc) {
+    call.mark(0);
+    call.rc = launch_ac_accumulate(call.st, B, d_rects, n, max_patches, xres, reset ? 1 : 0);
+    call.mark(1);
+  }
+  return call.finish(stats, 1, {0, 1}, {}, {0, 1});
+}
+
+int fjgpu_accumulate_tile_error(int device, int xres, int yres, const int32_t *rects, int n_rects, const fjgpu_accum_state *state,
+    float lum_floor, float *errors_out, void *hip_stream, fjgpu_stats *stats)
+{
+  ImageCall call("fjgpu_accumulate_tile_error", hip_stream);
+  const std::string &f = call.f;
+  if (!state || !state->mean || !state->m2 || !state->count || !errors_out)
+    return fail(FJGPU_EINVAL, f + ": null argument (state, its mean, m2 and count, and errors_out are required)");
+  std::vector<int32_t> list;
+  uint32_t max_patches = 0;
+  if (const int e = ac_check_rects(f, xres, yres, rects, n_rects, &list, &max_patches)) return e;
+  if (!(std::isfinite(lum_floor) && lum_floor > 0.f)) return fail(FJGPU_EINVAL, f + ": lum_floor must be finite and > 0");
+  if ((uintptr_t) state->mean & 15u) return fail(FJGPU_EINVAL, f + ": the state's mean must be 16-byte aligned");
+  if (const int e = call.open(device)) return e;
+  const int n = (int) (list.size() / 4);
+  fjgpu_stats none;
+  std::memset(&none, 0, sizeof(none));
+  if (n == 0) { if (stats) *stats = none; return 0; }
+  DeviceBuffers W;
+  const int32_t *d_rects = nullptr;
+  float *d_err = nullptr;
+  if (W.upload(list.data(), list.size(), &d_rects) || W.alloc((size_t) n, &d_err)) return fail(FJGPU_ENOMEM, f + ": device allocation failed");
+  call.start(2);
+  if (!call.rc) {
+    call.mark(0);
+    call.rc = launch_ac_tile_error(call.st, state->mean, state->m2, state->count, d_rects, n, xres, lum_floor, d_err);
+    if (!call.rc && hipMemcpyAsync(errors_out, d_err, sizeof(float) * (size_t) n, hipMemcpyDeviceToHost, call.st) != hipSuccess) call.rc = -1;
+    call.mark(1);
+  }
+  return call.finish(stats, 1, {0, 1}, {}, {0, 1});
 }
 
 }  // extern "C"

@@ -68,9 +68,17 @@ void SamplerMargin(const fj_render_desc &r, int margin[2])
   margin[1] = (int) std::ceil((((double) r.filter_h - 1) * r.rate_y) * .5);
 }
 
-void XorShiftTable(size_t n, std::vector<double> *out)
+void XorShiftTable(size_t n, std::vector<double> *out) { XorShiftTableSeeded(0u, n, out); }
+
+// seed 0: the default-constructed state (src/fj_random.cc:10-16), NOT XorShift(0); else XorShift(unsigned seed), src/fj_random.cc:18-24
+void XorShiftTableSeeded(unsigned seed, size_t n, std::vector<double> *out)
 {
   uint32_t s0 = 123456789u, s1 = 362436069u, s2 = 521288629u, s3 = 88675123u;
+  if (seed != 0u) {
+    uint32_t st[4], s = seed;
+    for (uint32_t i = 0; i < 4; i++) st[i] = s = 1812433253U * (s ^ (s >> 30)) + i;
+    s0 = st[0]; s1 = st[1]; s2 = st[2]; s3 = st[3];
+  }
   out->resize(n);
   for (size_t i = 0; i < n; i++) {
     const uint32_t t = s0 ^ (s0 << 11);
@@ -108,6 +116,15 @@ void fjgpu_host_xorshift_f01(int n, double *out)
   fjgpu::XorShiftTable((size_t) (n > 0 ? n : 0), &t);
   for (int i = 0; i < n; i++) out[i] = t[i];
 }
+
+void fjgpu_host_xorshift_f01_seeded(unsigned seed, int n, double *out)
+{
+  std::vector<double> t;
+  fjgpu::XorShiftTableSeeded(seed, (size_t) (n > 0 ? n : 0), &t);
+  for (int i = 0; i < n; i++) out[i] = t[i];
+}
+
+int32_t fjgpu_host_seeded_tile_id(unsigned seed, int32_t tile_id) { return (int32_t) fjgpu::SeededTileId(tile_id, seed); }
 
 void fjgpu_host_sampler_margin(const fj_render_desc *r, int32_t *margin)
 {

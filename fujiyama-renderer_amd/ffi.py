@@ -134,6 +134,18 @@ class TemporalClamp(C.Structure):      # fjgpu_temporal_clamp
     _fields_ = [("radius", C.c_int32), ("gamma", C.c_float), ("stop_at_ids", C.c_int32), ("_pad", C.c_int32), ("amount", C.c_void_p)]
 
 
+class AccumState(C.Structure):         # fjgpu_accum_state: DEVICE pointers
+    _fields_ = [(n, C.c_void_p) for n in ("mean", "m2", "count")]
+
+
+# fjgpu_accumulate(device, xres, yres, rects, n_rects, color, state, reset, variance_out, stream, stats)
+ACCUMULATE_ARGTYPES = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(AccumState), C.c_int, C.c_void_p, C.c_void_p,
+                       C.POINTER(GpuStats)]
+# fjgpu_accumulate_tile_error(device, xres, yres, rects, n_rects, state, lum_floor, errors_out, stream, stats)
+ACCUMULATE_TILE_ERROR_ARGTYPES = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(AccumState), C.c_float, C.c_void_p, C.c_void_p,
+                                  C.POINTER(GpuStats)]
+
+
 class RenderStats(C.Structure):        # fj_render_stats
     _fields_ = [("render_seconds", C.c_double), ("prepare_seconds", C.c_double), ("rays", RayCounts)]
 

@@ -439,9 +439,13 @@ int fjgpu_scene_view(const fjgpu_scene *scene, const fj_render_desc *render, fjg
  *
  * Limits.  Static scenes, a static camera per frame and the fixed-grid sampler: those of the AOV pass, whose buffers this reads.  Nothing
  * that moves with the camera on a surface is reprojected -- reflections, refractions, highlights, shadows of moving lights: the colour history
- * of a glass pixel follows the glass surface, not what is seen through it.  The sampler has no seed: two frames from the same camera are
- * identical and accumulating them gains nothing; the gain comes from the sub-pixel motion of a moving camera (a seed for the sampler and
- * the shaders' draws would be a change to the production path).  There is no Si* entry: the reference's interface has no such call. */
+ * of a glass pixel follows the glass surface, not what is seen through it.  Two frames from the same camera under the same "sampler_seed" (fjgpu_set_option)
+ * are identical and accumulating them gains nothing; under different seeds they are independent draws.  A standing camera fetches its
+ * history at the pixel it came from only if `position` is the hit through the pixel's centre: fjgpu_render_aov's position is the hit of the
+ * pixel's nearest own sample, 0.28 pixels from the centre on average in the 64 x 48 Cornell box, and with it the history is resampled once
+ * per frame (tests/test_gpu_accumulate.py has the figures; gpu.TemporalDenoiser passes a point on the centre's ray where it reseeds or the
+ * camera has not moved, and then keys the fetch by the pixel, since f32's rounding of the point leaves a neighbour tap of weight 2e-6).  The exact running
+ * mean of a view that stands is fjgpu_accumulate below.  There is no Si* entry: the reference's interface has no such call. */
 typedef struct fjgpu_temporal_history {   /* DEVICE pointers, row-major xres*yres */
   float *color;        /* [4]  accumulated RGBA                                  */
   float *moments;      /* [2]  first and second moment of (demodulated) luminance */
@@ -508,7 +512,62 @@ int fjgpu_denoise_temporal_clamped(int device, const fjgpu_temporal_desc *desc, 
     /* out            */ const fjgpu_temporal_history *next, float *variance_out /* [yres][xres] or NULL */,
     void *hip_stream, fjgpu_stats *stats);
 
-/* Tunables (all have defaults): "batch_tiles" tiles per wavefront batch, "batch_samples" samples per batch where batch_tiles is 0
+/* Progressive accumulation: the running mean of frames of ONE view that differ only in their "sampler_seed" (fjgpu_set_option), the
+ * variance of that mean per pixel, and its reduction to one error per tile -- so that a frame can be refined by rendering it again, and
+ * only the tiles that have not converged are rendered again (the tile list of fjgpu_render_tiles).  Device buffers in and out; no scene
+ * handle.  csrc/device/fjgpu_accum_math.h is the one source of the arithmetic (kernels, host twin of the CPU tests;
+ * tests/accumulate_model.py restates it): f32 without fused multiply-adds in the order written here, the tile's sum alone in f64.
+ *
+ * fjgpu_accumulate, for every pixel of a listed rectangle with new colour x (RGBA) and state (mean[4], m2, count):
+ *   reset      != 0: the state read counts as zero, whatever is stored (NaN included).
+ *   skip       a channel of x that is not finite: the state stays as read (as zero under reset, and zero is then what is stored) -- a
+ *              firefly NaN must not poison the mean.
+ *   update     n = count + 1;  mean_k' = mean_k + (x_k - mean_k) / n for the four channels;  with l = l(x.rgb) and m = l(mean.rgb) of the mean
+ *              BEFORE the update (l of fjgpu_denoise_variance: it is linear, so the luminance mean is not a plane of its own):
+ *              d = l - m;  m' = m + d / n;  m2' = m2 + d * (l - m');  count' = n.
+ *   variance   variance_out = count' >= 2 ? m2' / (count' * (count' - 1)) : 0 -- the variance of the MEAN, the quantity
+ *              fjgpu_denoise_variance takes as variance_in (of a skipped pixel: from the state it keeps).
+ * fjgpu_accumulate_tile_error, one value per listed rectangle: e_p = sqrtf(variance as above) / max(l(mean.rgb), lum_floor) per pixel; the
+ * f64 sum of e_p over the rectangle in a fixed order (fjgpu_accum_math.h; a serial sum differs by the rounding of f64 sums), divided by the
+ * pixel count and rounded to f32.  A rectangle with a pixel of count < 2 has the error +INFINITY.  Only n_rects floats cross to the host.
+ *
+ * rects: HOST [n_rects][4] = xmin ymin xmax ymax (fjgpu_tile_rect's), each non-empty and inside the frame, no two overlapping (not
+ * checked: a pixel in two rectangles is updated by two threads); NULL: the whole frame, n_rects is not read; n_rects 0: nothing is done.
+ * Pixels outside the rectangles are neither read nor written, in any buffer.  color must not overlap the state, variance_out neither the
+ * state nor color; color and state->mean are 16-byte aligned.  One launch of k_ac_accumulate (blocks of 16 x 16 pixels over (rectangle,
+ * patch), about 64 bytes per pixel, no LDS) or k_ac_tile_error (one block per rectangle: wave butterflies and one LDS step); no atomics,
+ * no scratch memory.  Work is enqueued on `hip_stream` and the call returns after the stream has been synchronised.  stats (may be NULL):
+ * resolve_ms = total_ms, batches = 1.
+ * Errors, all decided before any device call, FJGPU_EINVAL with a message that starts with the entry's name: a NULL color, state, member of
+ * the state or errors_out; a resolution that is not positive; n_rects < 0; a rectangle that is empty or not inside the frame; overlapping
+ * buffers (fjgpu_accumulate); a lum_floor that is not finite and > 0 (fjgpu_accumulate_tile_error); a misaligned color or mean; more than
+ * 2^31 - 1 blocks.  FJGPU_ENODEV when no device is visible.
+ *
+ * Limits.  Frames are weighted alike: no inverse-variance weighting.  The seed is a single scene's: fjgpu_render_frame_multi and
+ * fjgpu_scene_create_multi's replicas are not seeded together (each replica keeps its own option, default 0).  There is no Si* or
+ * bin/scene entry.  The CPU oracle has no seed: a seeded frame has no oracle render, only the oracle's trace of its camera rays. */
+typedef struct fjgpu_accum_state {   /* DEVICE, row-major xres*yres */
+  float *mean;    /* [4] running mean of RGBA             */
+  float *m2;      /* [1] Welford M2 of the luminance       */
+  float *count;   /* [1] frames accumulated in this pixel  */
+} fjgpu_accum_state;
+
+int fjgpu_accumulate(int device, int xres, int yres, const int32_t *rects /* HOST [n][4] xmin ymin xmax ymax, NULL = whole frame */,
+    int n_rects, const float *color /* [4] */, const fjgpu_accum_state *state, int reset, float *variance_out /* [1] or NULL */,
+    void *hip_stream, fjgpu_stats *stats);
+
+int fjgpu_accumulate_tile_error(int device, int xres, int yres, const int32_t *rects, int n_rects,
+    const fjgpu_accum_state *state, float lum_floor, float *errors_out /* HOST [n_rects] */, void *hip_stream, fjgpu_stats *stats);
+
+/* Tunables (all have defaults): "sampler_seed" 0..65535 (default 0; any other value: FJGPU_EINVAL naming the option and the range): the
+ * random streams of the beauty pass.  0: the reference's -- every call uploads and launches exactly what it did before the option
+ * existed.  s != 0: the jitter and time tables are the draws of the reference's seeded generator, XorShift(s) (src/fj_random.cc:18-24), in
+ * the layout of the unseeded tables, and the sample uid behind the pathtracing shader's, the area lights' and the motion's streams is
+ * that of tile id + 4096 s ("Random streams").  It applies alike to fjgpu_render_tiles, fjgpu_render_tiles_variance,
+ * fjgpu_render_frame, the three AOV entries, fjgpu_camera_samples and the adaptive sampler, which agree with each other under one seed;
+ * the scene's cached tables are rebuilt when the seed changes or the table grows, and not otherwise.  fjgpu_scene_query("sampler_seed")
+ * returns it.  With a jitter of 0, no pathtracing shader, no area light and no motion nothing is drawn and the seed changes nothing.
+ * "batch_tiles" tiles per wavefront batch, "batch_samples" samples per batch where batch_tiles is 0
  * (0, the default: as many as the memory budget holds -- fastest where frames repeat; a caller that renders one frame per scene
  * sets a few M: the work arena shrinks from ~110 GB to a few GB at the headline size and the cold frame starts sooner),
  * "count_nodes" 0/1 enable traversal event counters, "overlap_shadow" 0/1 run the shadow work of
@@ -635,6 +694,10 @@ int fjgpu_build_config(const char *name, double *value);
  * reference's golden vectors on a machine without a GPU. */
 void fjgpu_host_make_transform(int transform_order, int rotate_order, const double *trs9, double *M16, double *Minv16);
 void fjgpu_host_xorshift_f01(int n, double *out);
+/* the same under option "sampler_seed" = seed: seed 0 is fjgpu_host_xorshift_f01, else the first n draws of XorShift(seed) */
+void fjgpu_host_xorshift_f01_seeded(unsigned seed, int n, double *out);
+/* what the host writes into a tile's id under that seed (tile_id + 4096 seed; DESIGN.md 4, "Random streams") */
+int32_t fjgpu_host_seeded_tile_id(unsigned seed, int32_t tile_id);
 void fjgpu_host_sampler_margin(const fj_render_desc *render, int32_t *margin2);
 double fjgpu_host_camera_uv_size_y(double fov);
 
