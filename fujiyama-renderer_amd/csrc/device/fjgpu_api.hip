@@ -147,6 +147,9 @@ struct fjgpu_scene {
   unsigned long long hull_verdicts = 0;  // query "light_hull_verdicts": pairs the hull cones settled in the last render call (counting frames, option count_nodes; else 0)
   long count_all_shadow;           // option "count_all_shadow" (default 1): light records of weight zero reach the light loop, which counts their shadow rays as the
                                    // reference does; it never queues them (their colour is exactly zero), so nothing walks them.  0: k_shade drops such records (other counts)
+  long shade_first_touch = 1;      // option "shade_first_touch" (default 1): the camera level of a fixed-grid batch STORES its samples (ShadeParams.first_touch) and the
+                                   // batch's memset of d_accum is not issued; 0: memset, then atomic adds and the alpha store, as every other level
+  unsigned long long accum_memsets = 0;  // query "accum_memsets": batches of the last render call that cleared d_accum with a memset
   // queries "stack_peak" / "stack_peak_closest" / "stack_peak_shadow": the most entries any lane's traversal stack held in the launches of the
   // last render_* / trace call (counting instantiations only, option count_nodes; 0 without it)
   unsigned long long stack_peak_closest = 0, stack_peak_shadow = 0;
@@ -1298,6 +1301,8 @@ int fjgpu_scene_query(const fjgpu_scene *scene, const char *name, double *value)
         return 0;
       }
   }
+  // batches of the last render call whose samples were cleared by a memset (the adaptive sampler's, or every batch with option shade_first_touch 0)
+  if (n == "accum_memsets") { *value = (double) scene->accum_memsets; return 0; }
   if (n == "has_curves") { *value = scene->S.has_curves; return 0; }
   if (n == "has_motion") { *value = scene->S.has_motion; return 0; }
   return fail(FJGPU_EINVAL, "unknown query " + n);
@@ -1421,6 +1426,11 @@ int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value)
   if (n == "count_all_shadow") { scene->count_all_shadow = value != 0; return 0; }
   if (n == "light_cones") { scene->light_cones = value != 0; return 0; }
   if (n == "light_hulls") { scene->light_hulls = value != 0; return 0; }
+  if (n == "shade_first_touch") {
+    if (value != 0 && value != 1) return fail(FJGPU_EINVAL, "shade_first_touch: 0 (memset and atomic adds at the camera level) or 1 (one store per sample)");
+    scene->shade_first_touch = value;
+    return 0;
+  }
   if (n == "sampler_seed") {
     if (value < 0 || value > 65535) return fail(FJGPU_EINVAL, "sampler_seed: " + std::to_string(value) + " is outside 0..65535 (0: the unseeded streams)");
     scene->sampler_seed = value;      // (the tables follow at the next call that reads them: ensure_work)
@@ -1650,6 +1660,7 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   sc->stack_peak_closest = sc->stack_peak_shadow = 0;
   sc->hull_verdicts = 0;
+  sc->accum_memsets = 0;
 
   std::vector<fjgpu::TileRect> all;
   fjgpu::GenerateTiles(*r, &all);
@@ -1795,7 +1806,13 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
   shp.count_all_shadow = (int) sc->count_all_shadow;
   shp.ray_capacity = (uint32_t) cap_rays; shp.light_capacity = (uint32_t) cap_rays;
   shp.fc_in = nullptr; shp.fc_out = nullptr;
-  shp.next_keys = nullptr; shp.sort_bits = std::max(1, std::min(9, sc->ray_sort_bits)); shp.pad_ = 0;
+  shp.next_keys = nullptr; shp.sort_bits = std::max(1, std::min(9, sc->ray_sort_bits)); shp.first_touch = 0;
+  // FIRST TOUCH: the fixed-grid sampler queues every sample of the batch exactly once at level 0, entry i of a launch at chunk offset
+  // `off` being sample off + i (implicit camera rays by construction, explicit ones because camera_path writes sample = slot), and nothing adds to
+  // d_accum between the previous batch's resolve and this batch's level-0 shading launches: a batch ends with finish_shadow() -- the main stream waits
+  // for the shadow stream -- and its resolve, and the host synchronises with both before the next batch or call.  So level 0 stores its samples and
+  // the memset below is not needed.  (The adaptive sampler queues SOME samples per pass and reads the others: it keeps the memset.)
+  const bool first_touch = !adaptive && sc->shade_first_touch != 0;
   ray_sort_grid(sc->scene_box, shp.sort_bits, shp.sort_lo, shp.sort_scale);
   ShadowParams swp;
   swp.cos_half_pi = std::cos(3.14159265358979323846 / 2.);
@@ -1893,7 +1910,7 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
     }
     const uint32_t n_samples = off;
     if ((hipMemcpyAsync(sc->d_tiles, td.data(), sizeof(TileDesc) * nb, hipMemcpyHostToDevice, st)) != hipSuccess) { rc = -1; break; }
-    (void) hipMemsetAsync(sc->d_accum, 0, sizeof(float) * 4 * (size_t) n_samples, st);
+    if (!first_touch) { (void) hipMemsetAsync(sc->d_accum, 0, sizeof(float) * 4 * (size_t) n_samples, st); sc->accum_memsets++; }
     (void) hipMemsetAsync(sc->d_cnt, 0, sizeof(DCounters), st);
 
     // implicit camera rays (fjgpu_dev_shade.h): level 0 is rebuilt from the (u, v) table where it is needed
@@ -1986,8 +2003,10 @@ static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int
         shadow_pending[lb] = false;
         DScene Sl = S;
         if (implicit) { Sl.cam_uv = St.cam_uv; Sl.cam_slot0 = off; Sl.cam_tk = St.cam_tk; }
+        if (first_touch && level == 0) Sl.cam_slot0 = off;      // (explicit camera rays too: the sample of entry i)
         Sl.lrec_hair = sc->d_lhair[lb];
         ShadeParams shl = shp;
+        shl.first_touch = (first_touch && level == 0) ? 1 : 0;
         shl.next_keys = (can_emit && sc->ray_sort_bits > 0) ? sc->levels[level + 1].keys : nullptr;
         shl.fc_in = (!implicit && sc->levels[level].fc) ? sc->levels[level].fc + 3 * (size_t) off : nullptr;
         shl.fc_out = can_emit ? sc->levels[level + 1].fc : nullptr;

@@ -255,7 +255,10 @@ __device__ V3 bump_mapping(const DTexture &bump, V3 dPdu, V3 dPdv, float tu, flo
 // 10 M same-line atomics per C3 frame were most of the shading kernel's time.  Four appends one after the other -- each two
 // barriers and a returning atomic the whole block waits for -- were a third of a block's life on C4.)
 // Every thread of the block must call it.  A block's children sit in the queue as [diffuse | reflect | refract].
-struct AppendSlots { uint32_t light, c2, c0, c1; };
+struct AppendSlots {
+  uint32_t light, c2, c0, c1;
+  uint32_t base_light, n_light, base_rays, n_rays;    // the block's range in each queue (the same in every thread): staged output below
+};
 __device__ __forceinline__ AppendSlots block_append4(bool want_light, bool want2, bool want0, bool want1, DCounters *cnt, uint32_t *s_tmp)
 {
   constexpr int W = BLOCK / 64;
@@ -293,6 +296,8 @@ __device__ __forceinline__ AppendSlots block_append4(bool want_light, bool want2
   a.c2 = want2 ? baseR + before[1] + (uint32_t) __popcll(m2 & lt) : 0xffffffffu;
   a.c0 = want0 ? baseR + tot[1] + before[2] + (uint32_t) __popcll(m0 & lt) : 0xffffffffu;
   a.c1 = want1 ? baseR + tot[1] + tot[2] + before[3] + (uint32_t) __popcll(m1 & lt) : 0xffffffffu;
+  a.base_light = baseL; a.n_light = tot[0];
+  a.base_rays = baseR; a.n_rays = tot[1] + tot[2] + tot[3];
   return a;
 }
 
@@ -357,11 +362,73 @@ __device__ __forceinline__ void emit_child(const ChildRay &c, uint32_t slot, int
   next_paths[slot] = p;
 }
 
+// STAGED OUTPUT (FJ_SHADE_STAGE, the default).  block_append4 gives a block ONE contiguous range per queue, but a lane that stores its own 80-byte
+// light record, 48-byte ray and 36-byte path record does so with several 16- or 4-byte stores at the record stride: every store instruction of a
+// wave touches every line of the wave's span, partially.  Instead each thread writes its records into LDS at (slot - the block's base), and after one
+// barrier the block copies the range to global memory linearly: 16-byte stores for DLightRec and DRay (multiples of 16 bytes, ranges that start
+// 16-byte aligned), dword stores for DPath.  One buffer of BLOCK light records serves the three record types in turn; a block's children -- up to
+// three per thread -- go through it in windows of as many records as fit.  A range that crosses the queue's capacity is cut there (the threads
+// beyond it raise cnt->overflow as before).  The side arrays (next_keys, fc_out, lrec_hair) stay per-slot stores.
+#ifndef FJ_SHADE_STAGE
+#define FJ_SHADE_STAGE 1
+#endif
+constexpr uint32_t SHADE_STAGE_BYTES = BLOCK * sizeof(DLightRec);
+static_assert(sizeof(DLightRec) % 16 == 0 && sizeof(DRay) % 16 == 0 && sizeof(DPath) % 4 == 0, "the linear copies below move whole uint4 / dwords");
+
+// the block's records [0, n) of `bytes_per_rec` bytes each, as they sit in the staging buffer, to dst (n block-uniform; the caller's barriers around it)
+template <class Word>
+__device__ __forceinline__ void stage_copy_out(const unsigned char *s_stage, void *dst, uint32_t n, uint32_t bytes_per_rec)
+{
+  const uint32_t words = n * (bytes_per_rec / (uint32_t) sizeof(Word));
+  const Word *src = reinterpret_cast<const Word *>(s_stage);
+  Word *out = reinterpret_cast<Word *>(dst);
+  for (uint32_t k = threadIdx.x; k < words; k += BLOCK) out[k] = src[k];
+}
+
+// the capacity check and the side arrays of child `c` in slot `slot` (what emit_child does around its two records)
+__device__ __forceinline__ void child_side_arrays(const ChildRay &c, uint32_t slot, V3 o, const float *fc, DCounters *cnt, uint32_t capacity, const ShadeParams &sp)
+{
+  if (!c.want) return;
+  if (slot >= capacity) { cnt->overflow = 1; return; }
+  if (sp.next_keys) sp.next_keys[slot] = ray_sort_key(o, c.d, sp.sort_lo, sp.sort_scale, sp.sort_bits);
+  if (fc && (c.flags & 1u) && sp.fc_out) { float *fo = sp.fc_out + 3 * (size_t) slot; fo[0] = fc[0]; fo[1] = fc[1]; fo[2] = fc[2]; }
+}
+
+// child `c`, entry `rel` of the block's range, into the window [w0, w0 + wn) of the staging buffer: its ray ...
+__device__ __forceinline__ void stage_child_ray(const ChildRay &c, uint32_t rel, uint32_t w0, uint32_t wn, V3 o, unsigned char *s_stage)
+{
+  if (!c.want || rel - w0 >= wn) return;
+  DRay r;
+  r.o[0] = o.x; r.o[1] = o.y; r.o[2] = o.z;
+  r.d[0] = c.d.x; r.d[1] = c.d.y; r.d[2] = c.d.z;
+  reinterpret_cast<DRay *>(s_stage)[rel - w0] = r;           // (range: tmin by class below, tmax 1000)
+}
+
+// ... and its path record (the statements of emit_child)
+__device__ __forceinline__ void stage_child_path(const ChildRay &c, uint32_t rel, uint32_t w0, uint32_t wn, int cxt, const DPath &parent,
+    uint32_t sample, uint32_t uid, uint32_t tbits, uint32_t key, unsigned char *s_stage)
+{
+  if (!c.want || rel - w0 >= wn) return;
+  DPath p;
+  p.sample = sample;
+  p.T[0] = c.T[0]; p.T[1] = c.T[1]; p.T[2] = c.T[2];
+  p.cxt = (uint8_t) (cxt | (c.tmin < .0005f ? FJ_CXT_TMIN_1E4 : 0u));
+  p.ddepth = parent.ddepth + (cxt == CXT_DIFFUSE_RAY ? 1 : 0);
+  p.rdepth = parent.rdepth + (cxt == CXT_REFLECT_RAY ? 1 : 0);
+  p.tdepth = parent.tdepth + (cxt == CXT_REFRACT_RAY ? 1 : 0);
+  p.group = c.group;
+  p.flags = c.flags | tbits; p.rng = key; p.uid = uid;     // tbits: the sample's time index << 1
+  reinterpret_cast<DPath *>(s_stage)[rel - w0] = p;
+}
+
 // trace_surface's SurfaceInput setup + Shader::Evaluate for the device shaders.
 // Radiance is accumulated as throughput-weighted terms: every shader term of
 // the reference is linear in the radiance returned by its child SlTrace calls,
 // so `Cs = local + sum_k w_k * C_child_k` unrolls into per-path products
 // (DESIGN.md 6).
+#ifndef FJ_SHADE_LAZY
+#define FJ_SHADE_LAZY 1           // 1: the attributes of a hit are fetched behind its shader lookup, and only those the shader reads; 0: all of them for every hit
+#endif
 #ifndef FJ_SHADE_MINB
 #define FJ_SHADE_MINB 3           // resident blocks per CU the register budget is cut for (169 VGPRs as written = 2 waves; 164 = 3: C3 15.8 -> 14.8 ms, C4 269 -> 258)
 #endif
@@ -391,6 +458,7 @@ __global__ void __launch_bounds__(BLOCK, FJ_SHADE_MINB) k_shade(DScene S, ShadeP
   DLightHair lh;
   lr.kind = 0;
   uint32_t sample = 0, rng = 0, uid = 0, tbits = 0;
+  float4 first = make_float4(0.f, 0.f, 0.f, 0.f);      // first touch: what this entry's sample holds after the launch
 
   if (hit) {
     // (level 0 with implicit camera rays: nothing was written, ray and path state follow from the sample slot)
@@ -405,17 +473,30 @@ __global__ void __launch_bounds__(BLOCK, FJ_SHADE_MINB) k_shade(DScene S, ShadeP
     const DInstance *I = &S.instances[h.inst];
     const DPrimSet *P = &S.primsets[I->primset];
     const V3 ro = mk(r.o[0], r.o[1], r.o[2]), rd = mk(r.d[0], r.d[1], r.d[2]);
+    const bool is_curve = I->sh_type == FJ_PRIMSET_CURVE;
+
+    // --- shader lookup: ObjectInstance::GetShader (src/fj_object_instance.cc:177-191), by the face group of the hit triangle -- in FRONT of the
+    // attributes, because the shader decides which of them are read at all: a ConstantShader reads the texture coordinates when it has a texture
+    // and nothing else, a hit without a shader nothing (the dome behind the objects at level 0, and where most reflected rays end)
+    const int sg = (!is_curve && I->sh_face_group) ? FJ_G(int32_t, I->sh_face_group)[h.prim] : 0;
+    int sid;
+    if (sg < 0 || sg >= I->n_shaders) sid = I->shaders[0];
+    else { sid = I->shaders[sg]; if (sid < 0) sid = I->shaders[0]; }
+#if FJ_SHADE_LAZY
+    const bool full = sid >= 0 && S.shaders[sid].type != FJ_SHADER_CONSTANT;       // every attribute, the hit point, the instance matrices
+    const bool want_uv = full || (sid >= 0 && S.shaders[sid].texture >= 0);       // ... or the texture coordinates alone
+#else
+    const bool full = true, want_uv = true;
+#endif
 
     // instance matrices: host-built for static instances, evaluated at the ray's time for
     // time-sampled ones (the traversal did the same, so P and N belong to the same pose)
     const double *IM = I->M, *IMinv = I->Minv;
     double tm[12], tmi[12];
-    if (kMotion && I->xform >= 0) {
+    if (kMotion && full && I->xform >= 0) {
       xform_at(&S.xforms[I->xform], sample_time(S, p.flags >> 1), tm, tmi);
       IM = tm; IMinv = tmi;
     }
-    const V3 oo = xpoint(IMinv, ro);
-    const V3 od = xvector(IMinv, rd);
     V3 N = mk(0, 0, 0);
     float tu = 0.f, tv = 0.f;
     V3 dPdu = mk(0, 0, 0), dPdv = mk(0, 0, 0);
@@ -423,8 +504,8 @@ __global__ void __launch_bounds__(BLOCK, FJ_SHADE_MINB) k_shade(DScene S, ShadeP
     bool has_uv = false;
     float t0u = 0, t0v = 0, t1u = 0, t1v = 0, t2u = 0, t2v = 0;
     int i0 = 0, i1 = 0, i2 = 0;
-    int sg = 0;
-    if (I->sh_type == FJ_PRIMSET_CURVE) {
+    if (is_curve) {
+      if (full) {
       // --- Curve::ray_intersect attribute part (src/fj_curve.cc:211-229): dPdv = curve
       // derivative at v_hit, Cd = lerp of the end colours; N / uv / dPdu stay zero
       const size_t sl = (size_t) h.v;
@@ -444,16 +525,19 @@ __global__ void __launch_bounds__(BLOCK, FJ_SHADE_MINB) k_shade(DScene S, ShadeP
       Cd[0] = (1 - tl) * cd[0] + tl * cd[3];
       Cd[1] = (1 - tl) * cd[1] + tl * cd[4];
       Cd[2] = (1 - tl) * cd[2] + tl * cd[5];
-    } else {
+      }
+    } else if (want_uv) {
       // --- Mesh::ray_intersect attribute part (src/fj_mesh.cc:267-305) in object space
       // (the face's point indices: only where something is read through them -- a mesh whose normals sit per corner (sh_vN) and that has no
-      //  texture coordinates needs none of them here)
-      if (!I->sh_vN || I->sh_uv) { const FJ_GLOBAL int32_t *ix = FJ_G(int32_t, I->sh_indices) + 3 * (size_t) h.prim; i0 = ix[0]; i1 = ix[1]; i2 = ix[2]; }
-      V3 n0 = mk(0, 0, 0), n1 = n0, n2 = n0;
-      // compute_shading_normal, src/fj_mesh.cc:108-120: the mesh's per-corner ("vertex") normals where it has them, else its point normals
-      if (I->sh_vN) { const FJ_GLOBAL double *vn = FJ_G(double, I->sh_vN) + 9 * (size_t) h.prim; n0 = ld3(vn); n1 = ld3(vn + 3); n2 = ld3(vn + 6); }
-      else if (I->sh_N) { n0 = ld3(FJ_G(double, I->sh_N) + 3 * (size_t) i0); n1 = ld3(FJ_G(double, I->sh_N) + 3 * (size_t) i1); n2 = ld3(FJ_G(double, I->sh_N) + 3 * (size_t) i2); }
-      N = (1 - h.u - h.v) * n0 + h.u * n1 + h.v * n2;            // TriComputeNormal, src/fj_triangle.cc:44-49
+      //  texture coordinates needs none of them here, and a shader that reads the texture coordinates alone needs them for those only)
+      if ((full && !I->sh_vN) || I->sh_uv) { const FJ_GLOBAL int32_t *ix = FJ_G(int32_t, I->sh_indices) + 3 * (size_t) h.prim; i0 = ix[0]; i1 = ix[1]; i2 = ix[2]; }
+      if (full) {
+        V3 n0 = mk(0, 0, 0), n1 = n0, n2 = n0;
+        // compute_shading_normal, src/fj_mesh.cc:108-120: the mesh's per-corner ("vertex") normals where it has them, else its point normals
+        if (I->sh_vN) { const FJ_GLOBAL double *vn = FJ_G(double, I->sh_vN) + 9 * (size_t) h.prim; n0 = ld3(vn); n1 = ld3(vn + 3); n2 = ld3(vn + 6); }
+        else if (I->sh_N) { n0 = ld3(FJ_G(double, I->sh_N) + 3 * (size_t) i0); n1 = ld3(FJ_G(double, I->sh_N) + 3 * (size_t) i1); n2 = ld3(FJ_G(double, I->sh_N) + 3 * (size_t) i2); }
+        N = (1 - h.u - h.v) * n0 + h.u * n1 + h.v * n2;            // TriComputeNormal, src/fj_triangle.cc:44-49
+      }
       has_uv = I->sh_uv != nullptr;
       if (has_uv) {
         t0u = FJ_G(float, I->sh_uv)[2 * (size_t) i0]; t0v = FJ_G(float, I->sh_uv)[2 * (size_t) i0 + 1];
@@ -463,18 +547,16 @@ __global__ void __launch_bounds__(BLOCK, FJ_SHADE_MINB) k_shade(DScene S, ShadeP
         tu = (float) (tt * t0u + h.u * t1u + h.v * t2u);
         tv = (float) (tt * t0v + h.u * t1v + h.v * t2v);
       }
-      sg = I->sh_face_group ? FJ_G(int32_t, I->sh_face_group)[h.prim] : 0;
     }
-    Pw = oo + h.t * od;                                        // RayPointAt in object space
-    // --- ObjectInstance::RayIntersect back-transform (src/fj_object_instance.cc:231-240)
-    Pw = xpoint(IM, Pw);
-    N = normalize(xvector(IM, N));
-    dPdv = xvector(IM, dPdv);
-
-    // --- shader lookup: ObjectInstance::GetShader (src/fj_object_instance.cc:177-191)
-    int sid;
-    if (sg < 0 || sg >= I->n_shaders) sid = I->shaders[0];
-    else { sid = I->shaders[sg]; if (sid < 0) sid = I->shaders[0]; }
+    if (full) {
+      const V3 oo = xpoint(IMinv, ro);
+      const V3 od = xvector(IMinv, rd);
+      Pw = oo + h.t * od;                                        // RayPointAt in object space
+      // --- ObjectInstance::RayIntersect back-transform (src/fj_object_instance.cc:231-240)
+      Pw = xpoint(IM, Pw);
+      N = normalize(xvector(IM, N));
+      dPdv = xvector(IM, dPdv);
+    }
 
     // pending pow(filter, t_hit) of a refraction child (glass_shader.cc:117-121)
     if (p.flags & 1u) {
@@ -680,19 +762,75 @@ __global__ void __launch_bounds__(BLOCK, FJ_SHADE_MINB) k_shade(DScene S, ShadeP
     }
     Os = (float) clampd(Os, 0, 1);
     float *acc = s_accum + 4 * (size_t) sample;
-    if (add_cs) {
-      const float r0 = p.T[0] * Cs[0], r1 = p.T[1] * Cs[1], r2 = p.T[2] * Cs[2];
-      if (r0 != 0.f) atomicAdd(acc + 0, r0);
-      if (r1 != 0.f) atomicAdd(acc + 1, r1);
-      if (r2 != 0.f) atomicAdd(acc + 2, r2);
+    if (sp.first_touch) {
+      // (what 0 + r by atomic left in the cleared sample: r, a NaN included; no add -- and so +0 -- for a term that compares equal to zero)
+      if (add_cs) {
+        const float r0 = p.T[0] * Cs[0], r1 = p.T[1] * Cs[1], r2 = p.T[2] * Cs[2];
+        first.x = r0 != 0.f ? r0 : 0.f; first.y = r1 != 0.f ? r1 : 0.f; first.z = r2 != 0.f ? r2 : 0.f;
+      }
+      first.w = Os;
+    } else {
+      if (add_cs) {
+        const float r0 = p.T[0] * Cs[0], r1 = p.T[1] * Cs[1], r2 = p.T[2] * Cs[2];
+        if (r0 != 0.f) atomicAdd(acc + 0, r0);
+        if (r1 != 0.f) atomicAdd(acc + 1, r1);
+        if (r2 != 0.f) atomicAdd(acc + 2, r2);
+      }
+      if ((p.cxt & 0x7fu) == CXT_CAMERA_RAY) acc[3] = Os;   // one camera ray per sample
     }
-    if ((p.cxt & 0x7fu) == CXT_CAMERA_RAY) acc[3] = Os;   // one camera ray per sample
   }
+  // FIRST TOUCH (ShadeParams.first_touch): entry i of a camera level's launch is sample cam_slot0 + i, its only camera ray, and nothing has
+  // added to the sample since the last batch was resolved.  So the launch does not add to cleared samples, it stores them: one 16-byte store per
+  // entry -- the hit's own radiance and alpha, zeros for a miss -- in place of the batch's memset, three atomics and a 4-byte store.  Whatever
+  // adds to a sample (the light loops, the deeper levels) is launched behind this kernel.
+  if (sp.first_touch && active) reinterpret_cast<float4 *>(s_accum)[(size_t) S.cam_slot0 + i] = first;
 
   // ---- compaction: ballot + prefix count, one atomic per block and queue
   __shared__ uint32_t s_tmp[4 * (BLOCK / 64) + 2];
   const AppendSlots slots = block_append4(want_light, c2.want, c0.want, c1.want, cnt, s_tmp);
   const uint32_t lslot = slots.light;
+#if FJ_SHADE_STAGE
+  __shared__ __attribute__((aligned(16))) unsigned char s_stage[SHADE_STAGE_BYTES];
+  // (every count and base below is the same in every thread of the block: the barriers sit in uniform control flow)
+  if (slots.n_light) {
+    if (want_light) {
+      reinterpret_cast<DLightRec *>(s_stage)[lslot - slots.base_light] = lr;
+      if (lslot < sp.light_capacity) { if ((lr.kind & 1) && S.lrec_hair) S.lrec_hair[lslot] = lh; }
+      else cnt->overflow = 1;
+    }
+    __syncthreads();
+    const uint32_t room = slots.base_light < sp.light_capacity ? sp.light_capacity - slots.base_light : 0u;
+    stage_copy_out<uint4>(s_stage, lrecs + slots.base_light, slots.n_light < room ? slots.n_light : room, (uint32_t) sizeof(DLightRec));
+    if (slots.n_rays) __syncthreads();       // (the buffer is written again below)
+  }
+  if (slots.n_rays && next_rays) {
+    const uint32_t rel2 = slots.c2 - slots.base_rays, rel0 = slots.c0 - slots.base_rays, rel1 = slots.c1 - slots.base_rays;
+    child_side_arrays(c2, slots.c2, Pw, nullptr, cnt, sp.ray_capacity, sp);
+    child_side_arrays(c0, slots.c0, Pw, nullptr, cnt, sp.ray_capacity, sp);
+    child_side_arrays(c1, slots.c1, Pw, fc1, cnt, sp.ray_capacity, sp);
+    const uint32_t room = slots.base_rays < sp.ray_capacity ? sp.ray_capacity - slots.base_rays : 0u;
+    const uint32_t n_out = slots.n_rays < room ? slots.n_rays : room;           // (the block's range, cut at the queue's capacity)
+    constexpr uint32_t RW = SHADE_STAGE_BYTES / sizeof(DRay), PW = SHADE_STAGE_BYTES / sizeof(DPath);
+    for (uint32_t w0 = 0; w0 < slots.n_rays; w0 += RW) {
+      const uint32_t wn = slots.n_rays - w0 < RW ? slots.n_rays - w0 : RW;
+      stage_child_ray(c2, rel2, w0, wn, Pw, s_stage);
+      stage_child_ray(c0, rel0, w0, wn, Pw, s_stage);
+      stage_child_ray(c1, rel1, w0, wn, Pw, s_stage);
+      __syncthreads();
+      if (w0 < n_out) stage_copy_out<uint4>(s_stage, next_rays + slots.base_rays + w0, n_out - w0 < wn ? n_out - w0 : wn, (uint32_t) sizeof(DRay));
+      __syncthreads();
+    }
+    for (uint32_t w0 = 0; w0 < slots.n_rays; w0 += PW) {
+      const uint32_t wn = slots.n_rays - w0 < PW ? slots.n_rays - w0 : PW;
+      stage_child_path(c2, rel2, w0, wn, CXT_DIFFUSE_RAY, p, sample, uid, tbits, 4 * rng + 1, s_stage);
+      stage_child_path(c0, rel0, w0, wn, CXT_REFLECT_RAY, p, sample, uid, tbits, 4 * rng + 2, s_stage);
+      stage_child_path(c1, rel1, w0, wn, CXT_REFRACT_RAY, p, sample, uid, tbits, 4 * rng + 3, s_stage);
+      __syncthreads();
+      if (w0 < n_out) stage_copy_out<uint32_t>(s_stage, next_paths + slots.base_rays + w0, n_out - w0 < wn ? n_out - w0 : wn, (uint32_t) sizeof(DPath));
+      if (w0 + PW < slots.n_rays) __syncthreads();
+    }
+  }
+#else
   if (want_light) {
     if (lslot < sp.light_capacity) {
       lrecs[lslot] = lr;
@@ -703,6 +841,7 @@ __global__ void __launch_bounds__(BLOCK, FJ_SHADE_MINB) k_shade(DScene S, ShadeP
   emit_child(c2, slots.c2, CXT_DIFFUSE_RAY, Pw, p, nullptr, sample, uid, tbits, 4 * rng + 1, next_rays, next_paths, cnt, sp.ray_capacity, sp);
   emit_child(c0, slots.c0, CXT_REFLECT_RAY, Pw, p, nullptr, sample, uid, tbits, 4 * rng + 2, next_rays, next_paths, cnt, sp.ray_capacity, sp);
   emit_child(c1, slots.c1, CXT_REFRACT_RAY, Pw, p, fc1, sample, uid, tbits, 4 * rng + 3, next_rays, next_paths, cnt, sp.ray_capacity, sp);
+#endif
 }
 
 #endif

@@ -55,7 +55,10 @@ struct ShadeParams {
   const float *fc_in;
   float *fc_out;
   double sort_lo[3], sort_scale[3];
-  int32_t sort_bits, pad_;
+  int32_t sort_bits;
+  // 1: a camera level whose entry i is sample DScene.cam_slot0 + i, and nothing has added to the batch's samples yet: every entry STORES its sample
+  // (radiance and alpha of its hit, zeros for a miss) instead of adding to a cleared one, and the batch's memset is not issued
+  int32_t first_touch;
 };
 
 struct ShadowParams {

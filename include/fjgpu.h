@@ -576,7 +576,10 @@ int fjgpu_accumulate_tile_error(int device, int xres, int yres, const int32_t *r
  * of single-instance shadow groups with the per-light shadow cones built at scene creation (point lights, whole rays; same results, fewer
  * instructions); 0: every pair takes the box test; "light_hulls" 1/0 (default 1; only with light_cones on): that loop first settles the pairs
  * whose surface point lies outside the light's hull cone around the instance's mesh -- unoccluded, neither box-tested nor queued (static
- * single-instance mesh groups, point lights; same results, fewer shadow rays walked); 0: the box cones alone. Returns 0 or FJGPU_EINVAL. */
+ * single-instance mesh groups, point lights; same results, fewer shadow rays walked); 0: the box cones alone; "shade_first_touch" 1/0 (default 1;
+ * other values are refused): the camera level of a fixed-grid batch stores each sample once -- its hit's radiance and alpha, zeros for a
+ * miss -- and the batch's samples are not cleared first; 0: memset, then atomic adds and an alpha store (the same frame bit for bit; query
+ * "accum_memsets": batches of the last render call that took the memset, which the adaptive sampler always does). Returns 0 or FJGPU_EINVAL. */
 int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value);
 
 /* Process-wide options read by fjgpu_scene_create (which stands for the reference's
