@@ -1,6 +1,7 @@
 // fjgpu_api.hip -- C ABI of libfjgpu.so (include/fjgpu.h), the entry points that take a fjgpu_scene: device scene
-// residency, the wavefront batch loop, the ray-batch trace entry point, the AOV pass and the camera of a resident scene.
-// (the image-space passes, which take only buffers, are in fjgpu_image_api.hip)
+// residency, options and queries, the multi-device frame, the ray-batch trace entry point, the AOV pass and the camera of a resident scene.
+// (the beauty pass -- fjgpu_render_tiles, the work arena and the wavefront frame loop -- is in fjgpu_frame.hip, the scene record in
+// fjgpu_scene.h; the image-space passes, which take only buffers, are in fjgpu_image_api.hip)
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <map>
@@ -30,7 +31,7 @@
 #include "fjgpu_light_hull.h"
 #include "fjgpu_matte.h"
 #include "fjgpu_raysort.h"
-#include "fjgpu_sample_variance.h"
+#include "fjgpu_scene.h"
 #include "fjgpu_tlas.h"
 
 // the ONE error text of the library: every translation unit sets it through fjgpu::fail (fjgpu_api_common.h)
@@ -46,8 +47,6 @@ namespace {
 
 using fjgpu::fail;
 using fjgpu::DeviceBuffers;
-
-#define FJ_LREC_BUFS 4
 
 // ---- RCCL, loaded at first use (no link-time dependency: the single-device paths never need it).  The slab exchange of
 // fjgpu_render_frame_multi in RCCL's spelling -- ncclGroupStart / ncclSend / ncclRecv / ncclGroupEnd, SURVEY 8(e) -- beside the peer copy.
@@ -125,105 +124,6 @@ const std::vector<Rccl::comm_t> *rccl_comms(const std::vector<int> &devices, std
 
 }  // namespace
 
-struct fjgpu_scene {
-  int device;
-  DScene S;                        // device pointers inside
-  DeviceBuffers mem;               // scene-lifetime allocations
-  double cam_fov;
-  fj_camera_desc camera;           // the desc the scene was created with or last set to (fjgpu_scene_get_camera / fjgpu_scene_set_camera)
-  int n_light_samples;
-  // options
-  long batch_tiles;
-  long batch_samples = 0;          // option "batch_samples": samples per batch where batch_tiles is 0 (0: as many as the memory budget holds)
-  long aov_batch_samples = 0;      // option "aov_batch_samples": samples per batch of fjgpu_render_aov (0: FJ_AOV_BATCH_SAMPLES)
-  long render_calls = 0;           // fjgpu_render_tiles calls that rendered something (the first one sizes its batches for a cold start)
-  long count_events;
-  long light_cones = 1;            // option "light_cones" (default 1): the light loop of whole-ray launches settles box misses with the per-light shadow cones built at
-                                   // scene creation (fjgpu_light_cone.h); 0: the instantiation without them, the same pairs through the box test
-  int cone_rows = 0, cone_records = 0;   // queries "light_cone_rows" / "light_cone_records": groups with a row in the table, records of them with a plane
-  long light_hulls = 1;            // option "light_hulls" (default 1): the cone instantiation of the light loop settles the pairs outside the light's hull cone (fjgpu_light_hull.h)
-                                   // before the box is consulted: unoccluded, neither box-tested nor queued; 0: the box cones alone
-  int hull_rows = 0, hull_records = 0;   // queries "light_hull_rows" / "light_hull_records"
-  unsigned long long hull_verdicts = 0;  // query "light_hull_verdicts": pairs the hull cones settled in the last render call (counting frames, option count_nodes; else 0)
-  long count_all_shadow;           // option "count_all_shadow" (default 1): light records of weight zero reach the light loop, which counts their shadow rays as the
-                                   // reference does; it never queues them (their colour is exactly zero), so nothing walks them.  0: k_shade drops such records (other counts)
-  long shade_first_touch = 1;      // option "shade_first_touch" (default 1): the camera level of a fixed-grid batch STORES its samples (ShadeParams.first_touch) and the
-                                   // batch's memset of d_accum is not issued; 0: memset, then atomic adds and the alpha store, as every other level
-  unsigned long long accum_memsets = 0;  // query "accum_memsets": batches of the last render call that cleared d_accum with a memset
-  // queries "stack_peak" / "stack_peak_closest" / "stack_peak_shadow": the most entries any lane's traversal stack held in the launches of the
-  // last render_* / trace call (counting instantiations only, option count_nodes; 0 without it)
-  unsigned long long stack_peak_closest = 0, stack_peak_shadow = 0;
-  // work buffers (lazily sized)
-  std::unique_ptr<DeviceBuffers> work;
-  size_t work_samples, work_rays;
-  double *d_suv;
-  uint32_t *d_stk = nullptr;       // (tile id, index in the tile) per sample slot: DScene.cam_tk (scenes with uid-keyed random streams), or null
-  float *d_accum;
-  // adaptive grid sampler (allocated on first use, in the `work` arena)
-  double *d_aseen = nullptr, *d_afinal = nullptr;
-  uint8_t *d_apstate = nullptr, *d_acells = nullptr;
-  const void *a_owner = nullptr;
-  size_t a_samples = 0, a_cell_bytes = 0;
-  struct Level { DRay *rays; DPath *paths; size_t cap; uint32_t *keys; float *fc; };     // keys: sort keys of the level's rays (written by the shading kernel that emits them) or null;
-                                   // fc: filter colours of refraction children, 3 floats per slot (scenes with a glass / pathtracing shader) or null
-  bool has_filter_rays = false;    // some shader emits refraction children that carry a filter colour (DPath.flags bit 0)
-  std::vector<Level> levels;       // ray queue per recursion level (allocated on first use)
-  bool uses_sample_uid;            // some random stream or sample time of the scene is keyed by the sample's uid / index in its tile
-  int max_children;                // most child rays one shading event can emit in this scene
-  bool bounce_diffuse, bounce_reflect, bounce_refract;   // bounce types some shader of the scene emits
-  DHit *d_hits;
-  DLightRec *d_lrecs[FJ_LREC_BUFS];   // several buffers: the shadow stream consumes one while shading fills another (two are used without the overlap)
-  DLightHair *d_lhair[FJ_LREC_BUFS];  // only when the scene has a HairShader
-  int lrec_bufs = 2;                  // buffers allocated: 2, or FJ_LREC_BUFS once the overlap option is on
-  long overlap;                    // option "overlap_shadow": 0 off, 1 on, 2 by the batch size
-  bool overlap_now = false;        // ... what this render call does
-  size_t free_cached = 0;          // free HBM + this scene's own work arena, as of the last query
-  hipEvent_t ev_frame[2] = {nullptr, nullptr};   // frame start / end
-  long early_shadow = 0;           // FJGPU_EARLY_SHADOW = k > 0 (only where the light loops run on their own stream: small batches, a rank's share of a frame): the shadow
-                                   // queue is flushed after level k - 1's light loops, so that the one big any-hit walk runs BESIDE the deeper levels' closest-hit walks
-                                   // instead of after them.  Round 6, a rank's share: C3 0 / 1 / 2 / 3 -> 18.7 / 18.1-18.6 / 18.3 / 18.5 ms, C6 +0.3, arealights +0.3, C2
-                                   // 14.0 -> 15.1 with 1; switched on for single-instance shadow groups only, the SLOWEST of C3's eight shares went 17.95 -> 19.2 ms: off.
-  hipStream_t shadow_stream;       // light loop + shadow traversal run here, overlapping the next level's closest-hit work
-  hipStream_t read_stream = nullptr;   // the counters of a shading launch come back on this one while the main stream already runs the next level's walk
-  hipEvent_t ev_shaded = nullptr;
-  hipEvent_t ev_shadow_done[FJ_LREC_BUFS];    // shadow work reading d_lrecs[k] has finished
-  std::vector<hipEvent_t> ev_pool; // per-launch timing events (resolved at the end of the frame: no host sync per launch)
-  DShadowRay *d_squeue;
-  size_t squeue_rec_bytes = 0;       // bytes per entry the queue was allocated for (DShadowRayC or DShadowRay)
-  size_t squeue_cap;
-  uint32_t *d_join = nullptr; size_t join_cap = 0;   // DScene.shadow_join (work arena)
-  bool split_overflowed = false;   // the last render call overflowed a queue while rays were split
-  uint32_t split_kfac = 1;         // queue entries the host allows per (light record, light) pair when rays are split
-  bool split_shadow = false;       // the lean any-hit walk serves shadow groups of several instances: rays are queued per candidate instance
-  DCounters *d_cnt;
-  TileDesc *d_tiles;
-  double *d_jit, *d_tim;
-  size_t tab_len;
-  long sampler_seed = 0;           // option "sampler_seed" (0..65535, default 0: the streams of the reference): the jitter / time tables are those of
-                                   // XorShiftTableSeeded and TileDesc.id is SeededTileId of it, in every entry that draws ("Random streams")
-  long tab_seed = 0;               // the seed d_jit / d_tim were built with
-  int tiles_cap;
-  int stack_need;
-  double tri_record_bytes;         // 36 when every mesh is stored as f32 triangles, else 72
-  size_t blas_nodes;
-  // SAH treelet restructuring (fjgpu_lbvh.hip), summed over the device-built meshes of the scene
-  long blas_treelet_passes = 0;
-  unsigned long long blas_treelets_changed = 0;
-  double blas_sah_cost_initial = 0., blas_sah_cost = 0.;
-  size_t squeue_max;               // shadow-queue entries allowed by the memory budget
-  size_t batch_fit_samples = 0;    // 0, or the samples per batch the work buffers were cut down to when an allocation failed (not tried beyond again)
-  // ray-queue sort (fjgpu_raysort.hip): levels >= 1 of scenes with incoherent secondary rays
-  int ray_sort_bits = 0;           // grid bits per axis; 0 = rays are walked in queue order
-  double scene_box[6];             // union of the instances' world boxes (the sort's grid)
-  uint32_t *d_sort[4] = {nullptr, nullptr, nullptr, nullptr};   // -, keys_alt, -, perm (in the `work` arena)
-  void *d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0; size_t sort_cap = 0;
-  // frame-level buffers of fjgpu_render_frame_multi (lazily sized, freed with the scene)
-  float *d_frame = nullptr; size_t d_frame_n = 0;      // this device's framebuffer
-  float *d_slab = nullptr; size_t d_slab_n = 0;        // packed tiles: own ones (sender) / incoming (first device)
-  int32_t *d_rects = nullptr; size_t d_rects_n = 0;    // tile rectangles of a slab
-  fjgpu_batch_fn batch_fn = nullptr; void *batch_user = nullptr;   // fjgpu_set_batch_callback
-};
-
 static int grow(void **p, size_t *have, size_t want, size_t elem)
 {
   if (*have >= want && *p) return 0;
@@ -232,54 +132,6 @@ static int grow(void **p, size_t *have, size_t want, size_t elem)
   if (hipMalloc(p, std::max<size_t>(want, 1) * elem) != hipSuccess) return -1;
   *have = want;
   return 0;
-}
-
-// Option "overlap_shadow" (0 off, 1 on, 2 = by the size of the batch, the default): the light loops on a stream of their own, concurrent
-// with the NEXT recursion levels' closest-hit walks, and with only FJ_OVERLAP_CULL_BLOCKS resident blocks per CU so that they leave the
-// walks room.  It pays where the launches are small -- a rank's share of an 8-GPU frame, a small frame: the closest-hit walks of the deeper
-// levels are then a few long rays each (a launch per level: 0.7 ms of dependent fetches and nothing else, profiles/r04_wave_timeline_*.txt),
-// and the light loops' VALU work fits underneath: a rank's share of C3 20.9 -> 19.7 ms (profiles/r04_overlap_small_launches.txt).  A whole
-// 1080p frame on one GPU loses with it (123 -> 136 ms: its walks fill the chip for most of their time), so "by size" turns it on below
-// FJ_OVERLAP_MAX_SAMPLES samples per batch, for scenes whose shaders bounce.  (Round 1-3 kept it off: with the light loop at full
-// occupancy the two streams only took turns.  Walking level 0's shadow rays early, under the deeper levels, was measured too
-// (FJGPU_EARLY_SHADOW): the persistent walk fills every slot and the shading kernels of the deeper levels wait behind it: 20.3 ms.)
-#ifndef FJ_OVERLAP_MAX_SAMPLES
-#define FJ_OVERLAP_MAX_SAMPLES ((size_t) 24 << 20)    // (a quarter of a 1080p, 64 spp frame still loses with it: 35.5 -> 36.1 ms; an eighth gains)
-#endif
-#ifndef FJ_OVERLAP_CULL_BLOCKS
-#define FJ_OVERLAP_CULL_BLOCKS 1
-#endif
-static int enable_overlap(fjgpu_scene *sc)
-{
-  if (sc->shadow_stream) return 0;
-  // (FJGPU_OVERLAP_PRIO: the stream gets the LOWEST priority, so that its blocks only take the slots the main stream's kernels leave)
-  int prio_lo = 0, prio_hi = 0;
-  if (getenv("FJGPU_OVERLAP_PRIO") && hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) == hipSuccess && prio_lo != prio_hi) {
-    if (hipStreamCreateWithPriority(&sc->shadow_stream, hipStreamNonBlocking, prio_lo) != hipSuccess) { sc->shadow_stream = nullptr; return -1; }
-  }
-  else if (hipStreamCreateWithFlags(&sc->shadow_stream, hipStreamNonBlocking) != hipSuccess) { sc->shadow_stream = nullptr; return -1; }
-  for (int k = 0; k < FJ_LREC_BUFS; k++)
-    if (hipEventCreateWithFlags(&sc->ev_shadow_done[k], hipEventDisableTiming) != hipSuccess) return -1;
-  return 0;
-}
-
-// A render description the tiler can work on: positive sizes and a region inside the frame.
-// The reference only asserts region min < max (src/fj_tiler.cc:75-76) and would write outside
-// its framebuffer for a region past the frame; this is a public C ABI, so it is refused.
-static const char *bad_tiling(const fj_render_desc *r)
-{
-  if (r->xres <= 0 || r->yres <= 0 || r->tile_w <= 0 || r->tile_h <= 0)
-    return "bad render settings: resolution and tilesize must be positive";
-  if (r->region[0] < 0 || r->region[1] < 0 || r->region[2] > r->xres || r->region[3] > r->yres ||
-      r->region[0] >= r->region[2] || r->region[1] >= r->region[3])
-    return "bad render settings: render_region must be a non-empty rectangle inside the frame";
-  return nullptr;
-}
-static const char *bad_render(const fj_render_desc *r)
-{
-  if (const char *why = bad_tiling(r)) return why;
-  if (r->rate_x <= 0 || r->rate_y <= 0) return "bad render settings: pixelsamples must be positive";
-  return nullptr;
 }
 
 // FLAT groups (DFlat, fjgpu_dev_flat.h): when EVERY group of a scene with incoherent closest-hit rays holds only small static meshes built on
@@ -399,12 +251,12 @@ static bool build_flat_groups(const fjgpu::HostScene &hs, std::vector<HostFlat> 
 }
 
 static long g_ray_sort = -1;       // "ray_sort": grid bits per axis of the ray-queue sort (fjgpu_raysort.hip); 0 = off, -1 = by scene
-static long g_ray_sort_min = FJ_RAY_SORT_MIN;   // "ray_sort_min": smaller launches keep queue order
+long fjgpu::g_ray_sort_min = FJ_RAY_SORT_MIN;   // "ray_sort_min": smaller launches keep queue order
 static long g_device_tlas = 1;     // "device_tlas": the instance level of every group is built on the device (fjgpu_tlas.hip)
 static long g_tlas_verify = 0;     // "tlas_verify": ... and compared node for node with the host's build (scene creation fails on a difference)
 static long g_split_shadow = 1;    // "split_shadow": shadow rays into groups of several instances are queued once per candidate instance
                                    // (C2: any-hit walk 91 -> 54 ms, the light loop that now lists every candidate 18 -> 41 ms, frame 134 -> 121)
-static long g_compact_squeue = 1;  // "compact_squeue": 56-byte shadow-queue records (DShadowRayC) where the walks can rebuild direction and distance
+long fjgpu::g_compact_squeue = 1;  // "compact_squeue": 56-byte shadow-queue records (DShadowRayC) where the walks can rebuild direction and distance
 static long g_flat_groups = 1;     // "flat_groups": scenes with incoherent closest-hit rays whose groups hold only small static meshes walk ONE world-space tree per group
 static long g_curve_anyhit = 1;    // "curve_anyhit": curve scenes whose occluders are all opaque walk their shadow rays with k_shadow_anyhit_curves
 static long g_inst_lds = 1;        // "inst_lds": the walks keep the instance level of scenes that fit their budget in LDS (DInstEntry)
@@ -412,16 +264,18 @@ static long g_batch_tiles = 0;     // "batch_tiles": default of the per-scene op
 static long g_device_build = -1;   // "device_build": BLAS of meshes built on the GPU (fjgpu_lbvh.hip): 1 = clustering, 2 = radix tree; 0 = on the host; -1 = not set
 static long g_treelet_passes = 0;  // "blas_treelet_passes": 0 .. 8 passes of SAH treelet restructuring over a device-built BLAS (0 = off: today's trees)
 static long g_multi_exchange = 0;  // "multi_exchange": how fjgpu_render_frame_multi moves the devices' tile slabs: 0 one hipMemcpyPeer each, 1 RCCL grouped send / recv
-static long g_spec_walk = 1;       // "speculative_walk": the next recursion level's closest-hit walk is enqueued before the host has read how many rays it has (the walk reads the count itself)
-static long g_cold_start = 1;      // "cold_start": a scene's first render call uses batches of FJ_COLD_BATCH_SAMPLES samples (a small arena: a fast first frame)
+long fjgpu::g_spec_walk = 1;       // "speculative_walk": the next recursion level's closest-hit walk is enqueued before the host has read how many rays it has (the walk reads the count itself)
+long fjgpu::g_cold_start = 1;      // "cold_start": a scene's first render call uses batches of FJ_COLD_BATCH_SAMPLES samples (a small arena: a fast first frame)
 #ifndef FJ_COLD_BATCH_SAMPLES
 #define FJ_COLD_BATCH_SAMPLES ((size_t) 16 << 20)
 #endif
-static long g_cold_batch_samples = (long) FJ_COLD_BATCH_SAMPLES;      // "cold_batch_samples": ... of this many samples (0 = the default, 16 M)
+long fjgpu::g_cold_batch_samples = (long) FJ_COLD_BATCH_SAMPLES;      // "cold_batch_samples": ... of this many samples (0 = the default, 16 M)
 // "single_frame_build": scenes created while it is on render ONE frame (SiRenderScene): where device_build is not set they build on the GPU.
 // PER THREAD (the caller switches it on around ITS fjgpu_scene_create call, which reads it on the same thread): a scene created at the same time on
 // another thread is not touched by the toggle.
 static thread_local long g_single_frame = 0;
+// (the fjgpu:: ones above are those the frame loop reads: declared in fjgpu_scene.h)
+using fjgpu::g_ray_sort_min; using fjgpu::g_compact_squeue; using fjgpu::g_spec_walk; using fjgpu::g_cold_start; using fjgpu::g_cold_batch_samples;
 
 extern "C" {
 
@@ -1447,752 +1301,11 @@ int fjgpu_set_option(fjgpu_scene *scene, const char *name, long value)
     if (value && scene->work) {
       if (hipSetDevice(scene->device) != hipSuccess) return fail(FJGPU_ENODEV, "hipSetDevice");
       (void) hipDeviceSynchronize();
-      scene->work.reset();
-      scene->work_samples = scene->work_rays = 0; scene->tiles_cap = 0; scene->lrec_bufs = std::min(scene->lrec_bufs, 2); scene->squeue_rec_bytes = 0;
-      scene->sort_cap = 0; scene->a_owner = nullptr; scene->a_samples = 0; scene->a_cell_bytes = 0;
-      scene->d_aseen = scene->d_afinal = nullptr; scene->d_apstate = scene->d_acells = nullptr;
-      for (auto &L : scene->levels) { L.rays = nullptr; L.paths = nullptr; L.cap = 0; L.keys = nullptr; }
+      fjgpu::ForgetWorkArena(scene);
     }
     return 0;
   }
   return fail(FJGPU_EINVAL, "unknown option " + n);
-}
-
-}  // extern "C"
-
-namespace {
-
-struct BatchTile { fjgpu::TileRect r; int nx, ny; uint32_t offset; };
-
-
-// compact queue records (DShadowRayC, 56 bytes) where the consumers rebuild direction and distance: the lean and the curve any-hit walk,
-// point / dome lights, no motion
-bool scene_compact_squeue(const DScene &S)
-{
-  const bool lean = S.all_opaque && !S.has_curves && !S.has_motion && S.blas_base;
-  const bool curve_walk = S.has_curves && !S.has_motion && S.all_opaque && S.curve_anyhit && S.inst_lds && S.n_group_nodes <= FJ_INST_LDS_NODES_CURVES &&
-      S.n_instances <= FJ_INST_LDS_INSTS_CURVES && S.n_groups <= FJ_INST_LDS_GROUPS_CURVES && FJ_CURVE_QNODES && FJ_CLOSEST_QNODES;
-  return (lean || curve_walk) && !S.has_area && g_compact_squeue && !getenv("FJGPU_NO_COMPACT_SQUEUE");
-}
-
-int ensure_work(fjgpu_scene *sc, size_t samples, size_t rays, int tiles, size_t tab_len)
-{
-  const int want_bufs = sc->overlap_now ? FJ_LREC_BUFS : 2;
-  // the shadow queue is allocated at the record size the scene's walks read (56 or 80 bytes: 12 GB apart at the headline size); a scene
-  // that goes back to the long record (option compact_squeue switched off between calls) gets a new arena
-  const size_t rec_bytes = scene_compact_squeue(sc->S) ? sizeof(DShadowRayC) : sizeof(DShadowRay);
-  if (samples > sc->work_samples || rays > sc->work_rays || tiles > sc->tiles_cap || want_bufs > sc->lrec_bufs || rec_bytes > sc->squeue_rec_bytes) {
-    // the arena only GROWS: a reallocation for one reason (a small batch that wants the overlap's extra light-record buffers after a
-    // whole frame, a longer tile list) keeps every other dimension at the largest size seen, or callers that alternate whole frames
-    // with region / rank-share renders would free and reallocate tens of GB on every call
-    samples = std::max(samples, sc->work_samples); rays = std::max(rays, sc->work_rays); tiles = std::max(tiles, sc->tiles_cap);
-    const int old_bufs = sc->lrec_bufs;
-    // (the extra light-record buffers of the overlap mode belong to SMALL batches: an arena that grows to a larger batch -- the second call after
-    // a cold start -- takes what that batch wants, 2 x 80 B per ray, not the 4 the small one had: 21 GB at the headline size)
-    sc->lrec_bufs = samples > sc->work_samples ? want_bufs : std::max(sc->lrec_bufs, want_bufs);
-    sc->work.reset(new DeviceBuffers());
-    // the adaptive sampler's buffers lived in the old arena (a new arena may be allocated at the
-    // old one's address, so the owner pointer alone does not tell)
-    sc->sort_cap = 0; sc->a_owner = nullptr; sc->a_samples = 0; sc->a_cell_bytes = 0;
-    sc->d_aseen = sc->d_afinal = nullptr; sc->d_apstate = sc->d_acells = nullptr;
-    DeviceBuffers &W = *sc->work;
-    int e = 0;
-    e |= W.alloc(samples * 2, &sc->d_suv);
-    sc->d_stk = nullptr;
-    if (sc->uses_sample_uid && !sc->S.has_motion && !sc->S.cam_xform) e |= W.alloc(samples * 2, &sc->d_stk);      // (tile, index) per sample: implicit camera rays
-    e |= W.alloc(samples * 4, &sc->d_accum);
-    for (auto &L : sc->levels) { L.rays = nullptr; L.paths = nullptr; L.cap = 0; L.keys = nullptr; }
-    e |= W.alloc(rays, &sc->d_hits);
-    for (int k = 0; k < sc->lrec_bufs; k++) {
-      e |= W.alloc(rays, &sc->d_lrecs[k]);
-      sc->d_lhair[k] = nullptr;
-      if (sc->S.has_hair) e |= W.alloc(rays, &sc->d_lhair[k]);
-    }
-    // (rays queued once per candidate instance: room for twice the entries, or the light loop runs in many short launches)
-    // (sized for the light loop's WORST case -- every (record, light) pair survives the cull -- where the memory is there: the bound decides
-    // into how many launches the light loop of a level is cut, and each cut is a host round trip: a rank's share of C3 took three)
-    const size_t per_ray = std::max<size_t>(sc->split_shadow ? 16 : 8, std::min<size_t>(64, (size_t) std::max(1, sc->n_light_samples) * (sc->split_shadow ? 2 : 1)));
-    // (from the batch's own samples, not from the 8 M-entry floor small frames get for their RAY queues: a 64 x 64 render under a dome
-    // light of 64 samples allocated 40 GB here -- ADVICE round 4.  The bound only decides into how many launches the shadow walk is cut.)
-    const size_t lrec_bound = std::min<size_t>(rays, std::max<size_t>(samples * 4, (size_t) 1 << 16));
-    sc->squeue_cap = std::min<size_t>(lrec_bound * per_ray, sc->squeue_max) + 4096 * 1024;   // + one chunk per resident wave
-    { char *q = nullptr; e |= W.alloc(sc->squeue_cap * rec_bytes, &q); sc->d_squeue = (DShadowRay *) q; sc->squeue_rec_bytes = e ? 0 : rec_bytes; }
-    // join slots of shadow rays queued once per candidate instance (DScene.shadow_join): a ray that has one
-    // owns at least two queue entries
-    sc->d_join = nullptr; sc->join_cap = 0;
-    // (a slot per ray with >= 2 entries -- at most squeue_cap / 2 of them -- but the light loop's waves reserve slots JQ_CHUNK = 64 at a
-    // time and a chunk roll-over discards up to 63 of them, i.e. up to about half of what is reserved over a launch: sized for that
-    // worst case plus one chunk per resident wave and launch; 4 bytes per slot.  Beyond it the join area overflows like the queue
-    // does and the frame is rendered again without the split)
-    if (sc->split_shadow) { sc->join_cap = sc->squeue_cap + 1 + 32 * (persistent_threads() / 64) * 64; e |= W.alloc(sc->join_cap, &sc->d_join); }
-    e |= W.alloc(1, &sc->d_cnt);
-    e |= W.alloc((size_t) tiles, &sc->d_tiles);
-    if (e) { sc->work.reset(); sc->work_samples = sc->work_rays = 0; sc->tiles_cap = 0; sc->lrec_bufs = std::min(old_bufs, 2); sc->squeue_rec_bytes = 0; return -1; }
-    sc->work_samples = samples; sc->work_rays = rays; sc->tiles_cap = tiles;
-  }
-  if (tab_len > sc->tab_len) {
-    // the tables live with the scene (small): 3 draws per sample of the largest tile
-    std::vector<double> draws;
-    fjgpu::XorShiftTableSeeded((unsigned) sc->sampler_seed, 2 * tab_len, &draws);
-    if (sc->mem.upload(draws.data(), 2 * tab_len, const_cast<const double **>(&sc->d_jit))) return -1;
-    if (sc->mem.upload(draws.data(), tab_len, const_cast<const double **>(&sc->d_tim))) return -1;
-    sc->tab_len = tab_len;
-    sc->tab_seed = sc->sampler_seed;
-  } else if (sc->tab_seed != sc->sampler_seed) {
-    // another seed, the same length: the draws go into the tables that are there (no call is in flight: every render call ends synchronised)
-    std::vector<double> draws;
-    fjgpu::XorShiftTableSeeded((unsigned) sc->sampler_seed, 2 * sc->tab_len, &draws);
-    if (hipMemcpy(sc->d_jit, draws.data(), sizeof(double) * 2 * sc->tab_len, hipMemcpyHostToDevice) != hipSuccess) return -1;
-    if (hipMemcpy(sc->d_tim, draws.data(), sizeof(double) * sc->tab_len, hipMemcpyHostToDevice) != hipSuccess) return -1;
-    sc->tab_seed = sc->sampler_seed;
-  }
-  return 0;
-}
-
-// AdaptiveGridSampler buffers: per sample the value its users see when it holds an earlier
-// leaf's interpolation, the final (filtered) value, a state byte; per lattice cell a verdict
-int ensure_adaptive(fjgpu_scene *sc, size_t samples, size_t cell_bytes)
-{
-  // (the work buffers were just sized by ensure_work: these live in the same arena, which is
-  // replaced as a whole when it grows)
-  if (sc->a_owner == sc->work.get() && samples <= sc->a_samples && cell_bytes <= sc->a_cell_bytes) return 0;
-  DeviceBuffers &W = *sc->work;
-  if (W.alloc(samples * 4, &sc->d_aseen) || W.alloc(samples * 4, &sc->d_afinal) || W.alloc(samples, &sc->d_apstate) ||
-      W.alloc(cell_bytes, &sc->d_acells)) { sc->a_owner = nullptr; return -1; }
-  sc->a_owner = sc->work.get(); sc->a_samples = samples; sc->a_cell_bytes = cell_bytes;
-  return 0;
-}
-
-int ensure_level(fjgpu_scene *sc, int level, size_t cap)
-{
-  fjgpu_scene::Level &L = sc->levels[level];
-  if (L.cap >= cap) return 0;
-  DeviceBuffers &W = *sc->work;
-  if (W.alloc(cap, &L.rays) || W.alloc(cap, &L.paths)) return -1;   // older, smaller buffers stay owned by `work`
-  L.keys = nullptr;
-  L.fc = nullptr;
-  if (sc->has_filter_rays && level >= 1 && W.alloc(cap * 3, &L.fc)) return -1;
-  if (sc->ray_sort_bits > 0 && level >= 1 && W.alloc(cap, &L.keys)) return -1;
-  L.cap = cap;
-  return 0;
-}
-
-// scratch of the ray-queue sort for up to `cap` rays (lives in the work arena like the queues)
-int ensure_sort(fjgpu_scene *sc, size_t cap)
-{
-  if (sc->sort_cap >= cap) return 0;
-  DeviceBuffers &W = *sc->work;
-  sc->d_sort[0] = sc->d_sort[2] = nullptr;       // (keys come from the shading kernel; the values are the indices, implicit in the first pass)
-  if (W.alloc(cap, &sc->d_sort[1]) || W.alloc(cap, &sc->d_sort[3])) return -1;
-  sc->sort_tmp_bytes = ray_sort_temp_bytes((uint32_t) cap, sc->ray_sort_bits);
-  char *tmp = nullptr;
-  if (W.alloc(sc->sort_tmp_bytes, &tmp)) return -1;
-  sc->d_sort_tmp = tmp;
-  sc->sort_cap = cap;
-  return 0;
-}
-
-
-}  // namespace
-
-extern "C" {
-
-// fjgpu_render_tiles_variance's part of a call: where the variance of the listed tiles' pixels goes and, optionally, the albedo it is taken under
-struct SampleVarianceOut { float *variance; const float *albedo; float albedo_floor; };
-
-static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
-    float *d_fb, void *hip_stream, fjgpu_stats *stats, const SampleVarianceOut *sv = nullptr);
-
-static int render_tiles_retrying(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
-    float *d_fb, void *hip_stream, fjgpu_stats *stats, const SampleVarianceOut *sv)
-{
-  sc->split_overflowed = false;
-  int e = render_tiles_once(sc, r, tile_ids, n_tiles, d_fb, hip_stream, stats, sv);
-  if (e == FJGPU_ENOMEM && sc->split_overflowed) {
-    // rays queued once per candidate instance outgrew the host's bound on the shadow queue (a scene whose
-    // instance boxes overlap many times over): this scene goes back to whole rays and the tiles are rendered again
-    // (said once per scene, verbose or not: from here on the scene's frames take the slower path)
-    fprintf(stderr, "fjgpu: shadow queue overflow with rays split per candidate instance: rendering the tiles again without the split, "
-        "which stays off for this scene (option split_shadow)\n");
-    sc->split_shadow = false;
-    e = render_tiles_once(sc, r, tile_ids, n_tiles, d_fb, hip_stream, stats, sv);
-  }
-  if (!e) sc->render_calls++;
-  return e;
-}
-
-int fjgpu_render_tiles(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
-    float *d_fb, void *hip_stream, fjgpu_stats *stats)
-{
-  if (!sc || !r || !d_fb) return fail(FJGPU_EINVAL, "null argument");
-  return render_tiles_retrying(sc, r, tile_ids, n_tiles, d_fb, hip_stream, stats, nullptr);
-}
-
-int fjgpu_render_tiles_variance(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
-    float *d_fb, const float *d_albedo, float albedo_floor, float *d_variance, void *hip_stream, fjgpu_stats *stats)
-{
-  const std::string f = "fjgpu_render_tiles_variance";
-  if (!sc || !r || !d_fb || !d_variance) return fail(FJGPU_EINVAL, f + ": null argument (scene, render, framebuffer and variance are required)");
-  if (d_albedo && !(std::isfinite(albedo_floor) && albedo_floor > 0)) return fail(FJGPU_EINVAL, f + ": albedo_floor must be finite and > 0");
-  if (const char *why = bad_render(r)) return fail(FJGPU_EINVAL, f + ": " + why);
-  const size_t px = (size_t) r->xres * (size_t) r->yres;
-  auto overlaps = [](const float *a, size_t na, const float *b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-    return a0 < b0 + nb * sizeof(float) && b0 < a0 + na * sizeof(float);
-  };
-  if (overlaps(d_variance, px, d_fb, 4 * px) || (d_albedo && overlaps(d_variance, px, d_albedo, 3 * px)))
-    return fail(FJGPU_EINVAL, f + ": the variance buffer must not overlap the framebuffer or the albedo buffer");
-  // (the adaptive sampler resolves INTERPOLATED samples: they are not independent draws, and their spread is not the estimate's variance)
-  if (r->sampler_type == 1) return fail(FJGPU_EUNSUPPORTED, f + ": the adaptive sampler is not supported (its resolved samples are interpolated, not independent)");
-  const SampleVarianceOut sv = {d_variance, d_albedo, albedo_floor};
-  return render_tiles_retrying(sc, r, tile_ids, n_tiles, d_fb, hip_stream, stats, &sv);
-}
-
-static int render_tiles_once(fjgpu_scene *sc, const fj_render_desc *r, const int32_t *tile_ids, int n_tiles,
-    float *d_fb, void *hip_stream, fjgpu_stats *stats, const SampleVarianceOut *sv)
-{
-  const bool adaptive = r->sampler_type == 1;          // Renderer::SetSamplerType, src/fj_renderer.cc:487-499
-  if (r->sampler_type != 0 && !adaptive) return fail(FJGPU_EINVAL, "unknown sampler_type");
-  if (adaptive && (r->adaptive_max_subdivision < 0 || r->adaptive_max_subdivision > 8 || !(r->adaptive_subdivision_threshold >= 0)))
-    return fail(FJGPU_EINVAL, "adaptive_max_subdivision must be in [0, 8] and adaptive_subdivision_threshold >= 0");
-  if (const char *why = bad_render(r)) return fail(FJGPU_EINVAL, why);
-  HIP_TRY(hipSetDevice(sc->device));
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  sc->stack_peak_closest = sc->stack_peak_shadow = 0;
-  sc->hull_verdicts = 0;
-  sc->accum_memsets = 0;
-
-  std::vector<fjgpu::TileRect> all;
-  fjgpu::GenerateTiles(*r, &all);
-  std::vector<int> ids;
-  if (tile_ids) ids.assign(tile_ids, tile_ids + n_tiles);
-  else for (size_t i = 0; i < all.size(); i++) ids.push_back((int) i);
-  for (int id : ids) if (id < 0 || id >= (int) all.size()) return fail(FJGPU_EINVAL, "tile id out of range");
-
-  // samples of a tile: rate x rate per pixel plus the filter margin (fixed grid), or the
-  // corners of a lattice of 2^max_subdivision cells per pixel, margin in whole pixels (adaptive
-  // grid: count_samples_in_region / count_samples_in_margin, src/fj_adaptive_grid_sampler.cc:195-216)
-  int margin[2];
-  fjgpu::SamplerMargin(*r, margin);
-  const int a_div = adaptive ? 1 << r->adaptive_max_subdivision : 1;
-  if (adaptive) {
-    margin[0] = (int) std::ceil((double) r->filter_w - 1);
-    margin[1] = (int) std::ceil((double) r->filter_h - 1);
-  }
-  const size_t full_tile_samples = adaptive
-      ? (size_t) (a_div * (r->tile_w + 2 * margin[0]) + 1) * (size_t) (a_div * (r->tile_h + 2 * margin[1]) + 1)
-      : (size_t) (r->rate_x * r->tile_w + 2 * margin[0]) * (r->rate_y * r->tile_h + 2 * margin[1]);
-
-  // Batch size.  The persistent traversal kernels pay a tail per launch (ray costs are
-  // heavy tailed: the last waves finish long after the average one), so launches should be
-  // few and large: up to 160 M samples per batch -- a whole 1080p / 64 spp frame, ~80 GB of
-  // queues plus the shadow queue -- bounded by 40 % of the free HBM, unless told otherwise.
-  // Measured on C3: 4 M samples per batch 473 ms/frame, 80 M 392 ms, whole frame 390 ms; later,
-  // with a 196 ms frame: two batches 195.8 ms, one 192.9 ms.
-  // (asked once per arena: the query is a driver round trip, and a rank's share of a frame is 20 ms; an allocation that fails because
-  // somebody else took the memory meanwhile halves the batch below)
-  auto query_free = [&]() {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t) 16 << 30;
-    sc->free_cached = free_b + (sc->work ? sc->work->bytes : 0);   // our own work buffers are re-usable
-  };
-  if (!sc->work || sc->free_cached == 0) query_free();
-  size_t free_now = sc->free_cached;
-  // recursion levels this scene can reach: one queue per level, level = bounces so far, and a
-  // bounce type only occurs if some shader of the scene emits it
-  const int deepest = (sc->bounce_diffuse ? std::max(0, r->max_diffuse_depth) : 0) +
-      (sc->bounce_reflect ? std::max(0, r->max_reflect_depth) : 0) + (sc->bounce_refract ? std::max(0, r->max_refract_depth) : 0);
-  if (sc->levels.size() < (size_t) deepest + 1) sc->levels.resize((size_t) deepest + 1, fjgpu_scene::Level{nullptr, nullptr, 0, nullptr});
-  long bt = sc->batch_tiles;
-  // (a caller that renders ONE frame per scene -- SiRenderScene -- asks for batches of a few M samples: the work arena is then a few GB
-  // instead of ~110 GB at the headline size, and a cold frame does not wait for the driver to hand out, and clear, that much memory)
-  if (bt <= 0 && sc->batch_samples > 0) bt = std::max<long>(1, (long) ((size_t) sc->batch_samples / full_tile_samples));
-  // COLD START: a scene's FIRST call renders in batches of FJ_COLD_BATCH_SAMPLES samples whatever the memory would hold -- a work arena of ~14 GB
-  // instead of ~110 GB at the headline size: the first image is there after 0.15 s instead of the 2-5 s hipMalloc takes to hand out (and, after a process
-  // that has just ended, clear) the large arena (profiles/r05_e2e_scene.txt).  The second call sizes its batches by memory as before and pays for the
-  // growth once; a caller that renders one frame per scene never does.  ("cold_start" 0 / FJGPU_COLD_START=0: the first call already sizes by memory.)
-  if (bt <= 0 && sc->render_calls == 0 && g_cold_start && !adaptive) {
-    static const int on = [] { const char *e = getenv("FJGPU_COLD_START"); return e ? atoi(e) : 1; }();
-    if (on) bt = std::max<long>(1, (long) ((size_t) g_cold_batch_samples / full_tile_samples));
-  }
-  if (bt <= 0) {
-    const size_t per_sample = 32 + (size_t) (deepest + 1) * (sizeof(DRay) + sizeof(DPath) + (sc->has_filter_rays ? 12 : 0)) + sizeof(DHit) + 2 * sizeof(DLightRec) + (adaptive ? 72 : 0) +
-        ((sc->ray_sort_bits > 0 && deepest >= 1) ? 24 : 0);       // (the ray sort's keys, slots, permutation and scratch)
-    // (a scene without lights queues no shadow rays: the fifth of the HBM that queue may take goes to the ray queues --
-    // C4, nine recursion levels: 1010 -> 994 ms per frame.  Walking a whole level in one launch with per-level hit
-    // buffers and chunking only the shading was measured too: 130 -> ~50 closest-hit launches per frame, 1005 ms: dropped)
-    const double share = sc->n_light_samples == 0 ? .6 : .4;
-    const size_t target = std::min<size_t>((size_t) 160 << 20, (size_t) (share * (double) free_now) / per_sample);
-    bt = std::max<long>(1, (long) (target / full_tile_samples));
-  }
-  bt = std::min<long>(bt, (long) ids.size());
-  bt = std::min<long>(bt, (long) (((size_t) 1 << 31) / full_tile_samples));   // sample slots are 32-bit
-  // (a batch that did not fit last time -- a batch_tiles option beyond the memory -- is not tried again frame after frame: each failed attempt
-  // allocates and releases tens of GB, 15-20 s per frame measured with batch_tiles = 1020 on C4)
-  if (sc->batch_fit_samples && full_tile_samples * (size_t) bt > sc->batch_fit_samples) bt = std::max<long>(1, (long) (sc->batch_fit_samples / full_tile_samples));
-  if (bt < 1) bt = 1;
-  // light loops beside the next levels' closest-hit walks (option overlap_shadow): on, or by the size of the batch
-  sc->overlap_now = !adaptive && sc->n_light_samples > 0 && (sc->overlap == 1 || (sc->overlap == 2 && deepest >= 1 && full_tile_samples * (size_t) bt <= FJ_OVERLAP_MAX_SAMPLES));
-  if (sc->overlap_now && enable_overlap(sc)) sc->overlap_now = false;
-  if (!sc->read_stream) {      // (the speculative walk's counter read-back; without them the loop reads on the main stream as before)
-    if (hipStreamCreateWithFlags(&sc->read_stream, hipStreamNonBlocking) != hipSuccess) sc->read_stream = nullptr;
-    else if (hipEventCreateWithFlags(&sc->ev_shaded, hipEventDisableTiming) != hipSuccess) { (void) hipStreamDestroy(sc->read_stream); sc->read_stream = nullptr; sc->ev_shaded = nullptr; }
-  }
-  sc->squeue_max = std::max<size_t>((size_t) 4 << 20, std::min<size_t>((size_t) 512 << 20, (size_t) (.2 * (double) free_now) / sizeof(DShadowRay)));
-  if (sc->n_light_samples == 0) sc->squeue_max = (size_t) 4 << 20;
-  if (const char *e = getenv("FJGPU_SQUEUE_M")) sc->squeue_max = (size_t) std::max(1, atoi(e)) << 20;
-  size_t cap_samples = 0, cap_rays = 0;
-  bool requeried = false;
-  for (;;) {
-    cap_samples = full_tile_samples * (size_t) bt;
-    // one level holds at most the rays its parent chunk can emit (the scheduler chunks by
-    // max_children), so a queue never needs more than one entry per sample
-    // (small frames get queues of at least 8 M entries: with room for the worst-case fan-out the
-    // scheduler does not have to cut their levels into chunks of a few thousand rays)
-    cap_rays = std::max<size_t>(cap_samples, std::min<size_t>((size_t) 8 << 20, cap_samples * 16)) + 1024;
-    // the arena is about to be replaced: the shadow queue's bound follows what is free NOW, not what was free when the scene's first
-    // frame asked (other scenes or processes may have allocated since)
-    if (!requeried && sc->work && (cap_samples > sc->work_samples || cap_rays > sc->work_rays || (int) bt > sc->tiles_cap ||
-                                   (sc->overlap_now ? FJ_LREC_BUFS : 2) > sc->lrec_bufs)) {
-      requeried = true;
-      query_free();
-      free_now = sc->free_cached;
-      if (!getenv("FJGPU_SQUEUE_M") && sc->n_light_samples != 0)
-        sc->squeue_max = std::max<size_t>((size_t) 4 << 20, std::min<size_t>((size_t) 512 << 20, (size_t) (.2 * (double) free_now) / sizeof(DShadowRay)));
-    }
-    bool ok = ensure_work(sc, cap_samples, cap_rays, (int) bt, full_tile_samples) == 0;
-    // every reachable level now, so that a failure shrinks the batch instead of ending the frame
-    // (level 0 only where camera rays are explicit records: with implicit camera rays -- the rule of `implicit_cam` below -- nothing reads
-    // its 112 bytes per sample, 15 GB of a cold C3 frame's allocations)
-    const bool level0_implicit = !adaptive && sc->S.cam_xform == nullptr && (!sc->uses_sample_uid || !sc->S.has_motion) && !getenv("FJGPU_EXPLICIT_CAMERA_RAYS");
-    for (int l = level0_implicit ? 1 : 0; ok && l <= deepest; l++) ok = ensure_level(sc, l, cap_rays) == 0;
-    // ... and the ray sort's scratch (a failure here also halves the batch)
-    if (ok && sc->ray_sort_bits > 0 && deepest >= 1) ok = ensure_sort(sc, cap_rays) == 0;
-    if (ok) break;
-    (void) hipGetLastError();
-    if (bt == 1) return fail(FJGPU_ENOMEM, "device allocation failed for the wavefront work buffers");
-    // another process holds part of the HBM: half the batch (the old arena is released first)
-    sc->work.reset(); sc->work_samples = sc->work_rays = 0; sc->tiles_cap = 0; sc->free_cached = 0;
-    for (auto &L : sc->levels) { L.rays = nullptr; L.paths = nullptr; L.cap = 0; L.keys = nullptr; }
-    sc->a_owner = nullptr; sc->a_samples = 0; sc->a_cell_bytes = 0;
-    sc->sort_cap = 0;
-    bt = std::max<long>(1, bt / 2);
-    sc->batch_fit_samples = full_tile_samples * (size_t) bt;      // (at most this from now on; a smaller one that fails lowers it again)
-  }
-  // adaptive grid: split / leaf byte per lattice cell of every level (4/3 of the finest level)
-  const size_t a_cells0_cap = adaptive ? (size_t) bt * (size_t) (r->tile_w + 2 * margin[0]) * (size_t) (r->tile_h + 2 * margin[1]) : 0;
-  const size_t a_cell_bytes = a_cells0_cap * (((((size_t) 1) << (2 * (r->adaptive_max_subdivision + 1))) - 1) / 3);
-  if (adaptive && a_cells0_cap >= ((size_t) 1 << 32)) return fail(FJGPU_EINVAL, "too many lattice cells per batch: lower the batch_tiles option");
-  if (adaptive && ensure_adaptive(sc, cap_samples, a_cell_bytes))
-    return fail(FJGPU_ENOMEM, "device allocation failed for the adaptive sampler's buffers");
-
-  // camera (Renderer::preprocess_camera + Camera::compute_uv_size)
-  DScene S = sc->S;
-  const double aspect = r->xres / (double) r->yres;
-  S.cam_uv_size[1] = fjgpu::CameraUvSizeY(sc->cam_fov);
-  S.cam_uv_size[0] = S.cam_uv_size[1] * aspect;
-  S.time_tab = sc->d_tim; S.time_start = r->time_start; S.time_end = r->time_end;
-  S.lrec_hair = nullptr;      // set per launch (double buffered)
-
-  GenParams gp;
-  gp.rate_x = r->rate_x; gp.rate_y = r->rate_y; gp.margin_x = margin[0]; gp.margin_y = margin[1];
-  gp.udelta = 1. / (r->rate_x * r->xres);
-  gp.vdelta = 1. / (r->rate_y * r->yres);
-  gp.jitter = r->jitter;
-  gp.jittered = r->jitter > 0 ? 1 : 0;
-  gp.pad = 0;
-  ShadeParams shp;
-  shp.max_diffuse_depth = r->max_diffuse_depth; shp.max_reflect_depth = r->max_reflect_depth; shp.max_refract_depth = r->max_refract_depth;
-  shp.count_all_shadow = (int) sc->count_all_shadow;
-  shp.ray_capacity = (uint32_t) cap_rays; shp.light_capacity = (uint32_t) cap_rays;
-  shp.fc_in = nullptr; shp.fc_out = nullptr;
-  shp.next_keys = nullptr; shp.sort_bits = std::max(1, std::min(9, sc->ray_sort_bits)); shp.first_touch = 0;
-  // FIRST TOUCH: the fixed-grid sampler queues every sample of the batch exactly once at level 0, entry i of a launch at chunk offset
-  // `off` being sample off + i (implicit camera rays by construction, explicit ones because camera_path writes sample = slot), and nothing adds to
-  // d_accum between the previous batch's resolve and this batch's level-0 shading launches: a batch ends with finish_shadow() -- the main stream waits
-  // for the shadow stream -- and its resolve, and the host synchronises with both before the next batch or call.  So level 0 stores its samples and
-  // the memset below is not needed.  (The adaptive sampler queues SOME samples per pass and reads the others: it keeps the memset.)
-  const bool first_touch = !adaptive && sc->shade_first_touch != 0;
-  ray_sort_grid(sc->scene_box, shp.sort_bits, shp.sort_lo, shp.sort_scale);
-  ShadowParams swp;
-  swp.cos_half_pi = std::cos(3.14159265358979323846 / 2.);
-  swp.cos_pi = std::cos(3.14159265358979323846);
-  swp.pre_resolve = (S.all_opaque && !S.has_curves && !S.has_motion && S.blas_base) ? 1 : 0;   // the lean any-hit walk consumes the queue
-  swp.cast_shadow = r->cast_shadow;
-  // compact queue records (DShadowRayC) where the consumers rebuild direction and distance: the lean and the curve any-hit walk, point / dome lights, no motion
-  S.compact_squeue = scene_compact_squeue(S) ? 1 : 0;
-  S.pad_cs_ = 0;
-  swp.compact = S.compact_squeue;
-  swp.light_cones = (sc->light_cones && S.light_cones && S.cone_rows) ? 1 : 0;
-  swp.pad_ = 0;
-  swp.light_hulls = (swp.light_cones && sc->light_hulls && S.light_hulls && S.hull_rows) ? 1 : 0;
-  swp.queue_capacity = (uint32_t) sc->squeue_cap;
-  swp.join_capacity = (swp.pre_resolve && sc->split_shadow && sc->d_join) ? (uint32_t) sc->join_cap : 0u;
-  S.shadow_join = swp.join_capacity ? sc->d_join : nullptr;
-  S.shadow_queue_cap = (uint32_t) sc->squeue_cap;
-  ResolveParams rp;
-  rp.xres = r->xres; rp.yres = r->yres; rp.rate_x = r->rate_x; rp.rate_y = r->rate_y;
-  rp.npx_x = r->rate_x + 2 * margin[0]; rp.npx_y = r->rate_y + 2 * margin[1];
-  AdaptiveParams ap;
-  std::memset(&ap, 0, sizeof(ap));
-  if (adaptive) {
-    ap.D = r->adaptive_max_subdivision; ap.div = a_div;
-    ap.margin_x = margin[0]; ap.margin_y = margin[1];
-    ap.udelta = 1. / (a_div * r->xres);
-    ap.vdelta = 1. / (a_div * r->yres);
-    ap.jitter = r->jitter;
-    ap.jittered = r->jitter > 0 ? 1 : 0;
-    ap.threshold = (double) r->adaptive_subdivision_threshold;
-    ap.ray_capacity = (uint32_t) cap_rays;
-    // get_sampleset_in_pixel (src/fj_adaptive_grid_sampler.cc:172-193): a pixel's window starts
-    // div samples after its neighbour's and is div * (1 + 2 margin) + 1 samples wide
-    rp.rate_x = rp.rate_y = a_div;
-    rp.npx_x = a_div * (1 + 2 * margin[0]) + 1; rp.npx_y = a_div * (1 + 2 * margin[1]) + 1;
-  }
-  rp.fw = (double) r->filter_w; rp.fh = (double) r->filter_h;
-
-  fjgpu_stats acc;
-  std::memset(&acc, 0, sizeof(acc));
-  float ms = 0;
-  // Per-launch timing without a host round trip per launch: event pairs are recorded around
-  // every launch on its stream and turned into durations once, after the frame's last sync.
-  struct Span { size_t a, b; double *bucket; };
-  std::vector<Span> spans;
-  size_t ev_used = 0;
-  auto take_event = [&]() -> size_t {
-    if (ev_used == sc->ev_pool.size()) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return (size_t) -1; sc->ev_pool.push_back(e); }
-    return ev_used++;
-  };
-  auto timed = [&](hipStream_t stream, double *bucket, auto &&launch) -> int {
-    const size_t a = take_event(), b = take_event();
-    if (a == (size_t) -1 || b == (size_t) -1) return -1;
-    (void) hipEventRecord(sc->ev_pool[a], stream);
-    const int le = launch();
-    (void) hipEventRecord(sc->ev_pool[b], stream);
-    if (le) return le;
-    spans.push_back(Span{a, b, bucket});
-    return 0;
-  };
-  // The light loop and the shadow traversal of level L are independent of the closest-hit
-  // work of level L+1 (both consume what shading L produced), so they run on their own
-  // stream and fill each other's tails; light records are double buffered between them.
-  hipStream_t sst = (sc->overlap_now && sc->shadow_stream) ? sc->shadow_stream : st;
-  unsigned shade_seq = 0;
-  bool shadow_pending[FJ_LREC_BUFS] = {false, false, false, false};
-  const unsigned lrec_ring = (sst != st && sc->lrec_bufs >= FJ_LREC_BUFS) ? FJ_LREC_BUFS : 2;
-  int rc = 0;
-  hipEvent_t *ev_all = sc->ev_frame;      // (created once per scene: two driver calls less per frame)
-  if (!ev_all[0]) { HIP_TRY(hipEventCreate(&ev_all[0])); HIP_TRY(hipEventCreate(&ev_all[1])); }
-  (void) hipEventRecord(ev_all[0], st);
-
-  for (size_t b0 = 0; b0 < ids.size() && rc == 0; b0 += (size_t) bt) {
-    const int nb = (int) std::min<size_t>((size_t) bt, ids.size() - b0);
-    std::vector<TileDesc> td(nb);
-    uint32_t off = 0, max_ts = 0, cell_off = 0;
-    int max_px = 0, max_w0 = 0, max_h0 = 0;
-    for (int k = 0; k < nb; k++) {
-      const fjgpu::TileRect &t = all[ids[b0 + k]];
-      TileDesc &d = td[k];
-      d.xmin = t.xmin; d.ymin = t.ymin; d.xmax = t.xmax; d.ymax = t.ymax; d.id = fjgpu::SeededTileId(t.id, (unsigned) sc->sampler_seed);
-      d.nx = r->rate_x * (t.xmax - t.xmin) + 2 * margin[0];
-      d.ny = r->rate_y * (t.ymax - t.ymin) + 2 * margin[1];
-      d.cell_offset = cell_off; d.pad = 0;
-      if (adaptive) {
-        const int w0 = t.xmax - t.xmin + 2 * margin[0], h0 = t.ymax - t.ymin + 2 * margin[1];
-        d.nx = a_div * w0 + 1; d.ny = a_div * h0 + 1;
-        cell_off += (uint32_t) w0 * (uint32_t) h0;
-        max_w0 = std::max(max_w0, w0); max_h0 = std::max(max_h0, h0);
-      }
-      d.sample_offset = off;
-      off += (uint32_t) d.nx * (uint32_t) d.ny;
-      max_ts = std::max(max_ts, (uint32_t) d.nx * (uint32_t) d.ny);
-      max_px = std::max(max_px, (t.xmax - t.xmin) * (t.ymax - t.ymin));
-    }
-    const uint32_t n_samples = off;
-    if ((hipMemcpyAsync(sc->d_tiles, td.data(), sizeof(TileDesc) * nb, hipMemcpyHostToDevice, st)) != hipSuccess) { rc = -1; break; }
-    if (!first_touch) { (void) hipMemsetAsync(sc->d_accum, 0, sizeof(float) * 4 * (size_t) n_samples, st); sc->accum_memsets++; }
-    (void) hipMemsetAsync(sc->d_cnt, 0, sizeof(DCounters), st);
-
-    // implicit camera rays (fjgpu_dev_shade.h): level 0 is rebuilt from the (u, v) table where it is needed
-    // (scenes whose random streams are keyed by the sample's uid -- pathtracing shader, area lights -- get a (tile, index) table of 8 bytes per
-    // sample beside it; time-sampled motion keeps explicit rays: the walks read the sample's time from the path record)
-    const bool tk_cam = sc->uses_sample_uid && !S.has_motion && sc->d_stk != nullptr;
-    const bool implicit_cam = !adaptive && S.cam_xform == nullptr && (!sc->uses_sample_uid || tk_cam) && !getenv("FJGPU_EXPLICIT_CAMERA_RAYS");
-    if (!adaptive) {
-      rc = timed(st, &acc.gen_ms, [&]() {
-        return launch_gen_camera(st, S, gp, sc->d_tiles, nb, max_ts, sc->d_jit, sc->d_tim, sc->d_suv,
-            implicit_cam ? nullptr : sc->levels[0].rays, implicit_cam ? nullptr : sc->levels[0].paths, (implicit_cam && tk_cam) ? sc->d_stk : nullptr);
-      });
-      if (rc) break;
-      acc.rays.camera += n_samples;
-    }
-
-    // Depth-first wavefront schedule: the rays of one recursion level live in that
-    // level's queue; a level is consumed in chunks small enough that the children a
-    // chunk can emit (max_children per ray) fit the next level's queue, and that
-    // queue is drained completely before the next chunk is taken.  Memory is bounded
-    // by levels x capacity whatever the branching of the shaders (glass: 2 children,
-    // pathtracing: up to 3), while plastic-only scenes run whole levels at once.
-    // shadow-ray queue of this batch: the light loops of every level append, one traversal
-    // launch consumes it (flush) at the end of the batch or when it could overflow
-    const uint64_t sq_cap = sc->squeue_cap, sq_pad = shadow_queue_padding();
-    const uint64_t nl_q = (uint64_t) std::max(1, sc->n_light_samples) * (S.shadow_join ? sc->split_kfac : 1u);
-    uint64_t sq_bound = 0;             // upper bound of the entries reserved so far
-    bool sq_dirty = false;
-    shadow_queue_reset(sst, sc->d_cnt);
-    auto flush_shadow = [&](const DScene &Sx) -> int {
-      if (sq_dirty) {
-        const int fe = timed(sst, &acc.shadow_walk_ms, [&]() {
-          return launch_shadow_trace(sst, Sx, sc->d_squeue, sc->d_accum, sc->d_cnt, (int) sc->count_events);
-        });
-        if (fe) return fe;
-        acc.trace_launches++; acc.shadow_walk_launches++;
-        shadow_queue_reset(sst, sc->d_cnt);
-      }
-      sq_bound = 0; sq_dirty = false;
-      return 0;
-    };
-    // SPECULATIVE WALK (round 5): after the shading launch of a level the host needs two counters back -- how many children, how many light
-    // records -- before it can go on, and the device used to wait 40-145 us for that round trip at every level.  The children's closest-hit walk does
-    // not need the host to know: it is enqueued right behind the shading launch and reads its ray count from the counter itself (DScene.trace_n_dev,
-    // bounded by the chunk the host would have cut), while the counters come back on a stream of their own.  `walk_launched`: process() was called
-    // for rays whose first chunk is already being walked.
-    bool walk_launched = false;
-    static const bool spec_env = [] { const char *e = getenv("FJGPU_SPEC_WALK"); return e ? atoi(e) != 0 : true; }();
-    const bool speculate = g_spec_walk && spec_env && sc->ray_sort_bits <= 0 && sc->read_stream && sc->ev_shaded;
-    std::function<int(int, uint32_t)> process = [&](int level, uint32_t count) -> int {
-      // rays of the deepest reachable level cannot emit children (has_reached_bounce_limit):
-      // there is no next queue
-      const bool can_emit = level < deepest;
-      bool skip_walk = walk_launched;      // (the first chunk's walk)
-      walk_launched = false;
-      if (can_emit && ensure_level(sc, level + 1, cap_rays)) return fail(FJGPU_ENOMEM, "device allocation failed for a ray queue level");
-      const uint32_t kids = (uint32_t) std::max(1, sc->max_children);
-      const uint32_t chunk_max = kids <= 1 ? count : std::max<uint32_t>(1u, (uint32_t) (cap_rays / kids));
-      for (uint32_t off = 0; off < count; off += chunk_max) {
-        const uint32_t n = std::min(chunk_max, count - off);
-        const bool implicit = implicit_cam && level == 0;
-        const DRay *rays = implicit ? nullptr : sc->levels[level].rays + off;
-        const DPath *paths = implicit ? nullptr : sc->levels[level].paths + off;
-        (void) hipMemsetAsync(&sc->d_cnt->next_count, 0, sizeof(uint32_t) * 2, st);   // next_count + light_count
-        // secondary rays leave the shading kernel in emission order: walk them in (octant, cell) order
-        DScene St = S;
-        if (implicit) { St.cam_uv = sc->d_suv + 2 * (size_t) off; St.cam_slot0 = off; St.cam_tk = tk_cam ? sc->d_stk + 2 * (size_t) off : nullptr; }
-        int e = 0;
-        if (sc->ray_sort_bits > 0 && level >= 1 && (long) n >= g_ray_sort_min) {
-          if (ensure_sort(sc, cap_rays)) return fail(FJGPU_ENOMEM, "device allocation failed for the ray sort");   // (sized with the queues: cannot fail here)
-          // (the keys were written by the shading kernel that emitted these rays: ShadeParams.next_keys)
-          e = timed(st, &acc.sort_ms, [&]() {
-            return launch_ray_sort_keyed(st, sc->levels[level].keys + off, n, sc->ray_sort_bits, sc->d_sort[1], sc->d_sort[3],
-                sc->d_sort_tmp, sc->sort_tmp_bytes);
-          });
-          if (e) return e;
-          St.ray_perm = sc->d_sort[3];
-          acc.rays_sorted += n;
-        }
-        if (!skip_walk) {
-          e = timed(st, &acc.closest_ms, [&]() {
-            return launch_trace_closest(st, St, rays, paths, sc->d_hits, n, sc->d_cnt, (int) sc->count_events);
-          });
-          if (e) return e;
-          acc.trace_launches++; acc.closest_launches++;
-        }
-        skip_walk = false;
-        const unsigned lb = shade_seq++ % lrec_ring;   // light-record buffer of this shading call
-        if (shadow_pending[lb] && sst != st) (void) hipStreamWaitEvent(st, sc->ev_shadow_done[lb], 0);
-        shadow_pending[lb] = false;
-        DScene Sl = S;
-        if (implicit) { Sl.cam_uv = St.cam_uv; Sl.cam_slot0 = off; Sl.cam_tk = St.cam_tk; }
-        if (first_touch && level == 0) Sl.cam_slot0 = off;      // (explicit camera rays too: the sample of entry i)
-        Sl.lrec_hair = sc->d_lhair[lb];
-        ShadeParams shl = shp;
-        shl.first_touch = (first_touch && level == 0) ? 1 : 0;
-        shl.next_keys = (can_emit && sc->ray_sort_bits > 0) ? sc->levels[level + 1].keys : nullptr;
-        shl.fc_in = (!implicit && sc->levels[level].fc) ? sc->levels[level].fc + 3 * (size_t) off : nullptr;
-        shl.fc_out = can_emit ? sc->levels[level + 1].fc : nullptr;
-        e = timed(st, &acc.shade_ms, [&]() {
-          return launch_shade(st, Sl, shl, rays, paths, sc->d_hits, n, sc->d_accum,
-              can_emit ? sc->levels[level + 1].rays : nullptr, can_emit ? sc->levels[level + 1].paths : nullptr, sc->d_lrecs[lb], sc->d_cnt);
-        });
-        if (e) return e;
-        DCounters hc;
-        bool launched_next = false;
-        // (with the light loops on their own stream the ORDER of the launches decides who is resident first: level 0's light loop -- the big one -- must
-        // reach the device before level 1's walk fills it, or the two take turns instead of overlapping: C2 93.8 -> 97.3 ms with the walk first; from
-        // level 1 on the light loops are small and the round trip is what costs)
-        if (speculate && can_emit && (sst == st || level >= 1)) {
-          // the children's walk behind the shading launch, the counters back on the side stream (which waits for the shading launch only)
-          if (hipEventRecord(sc->ev_shaded, st) != hipSuccess) return -1;
-          DScene Sn = S;
-          Sn.trace_n_dev = &sc->d_cnt->next_count;
-          // (sized by what THIS launch can emit -- n rays, at most `kids` children each -- not by the queue's capacity: a deep level of a few
-          //  hundred rays no longer starts a full persistent grid whose waves read the count and leave)
-          const uint32_t chunk_cap = kids <= 1 ? (uint32_t) std::min<size_t>(cap_rays, 0xffffffffu) : std::max<uint32_t>(1u, (uint32_t) (cap_rays / kids));
-          const uint32_t next_chunk = (uint32_t) std::min<uint64_t>(chunk_cap, (uint64_t) n * kids);
-          e = timed(st, &acc.closest_ms, [&]() {
-            return launch_trace_closest(st, Sn, sc->levels[level + 1].rays, sc->levels[level + 1].paths, sc->d_hits, next_chunk, sc->d_cnt, (int) sc->count_events);
-          });
-          if (e) return e;
-          launched_next = true;
-          if (hipStreamWaitEvent(sc->read_stream, sc->ev_shaded, 0) != hipSuccess ||
-              hipMemcpyAsync(&hc, sc->d_cnt, sizeof(hc), hipMemcpyDeviceToHost, sc->read_stream) != hipSuccess || hipStreamSynchronize(sc->read_stream) != hipSuccess) return -1;
-        }
-        else if (hipMemcpyAsync(&hc, sc->d_cnt, sizeof(hc), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-        if (hc.overflow) { sc->split_overflowed = S.shadow_join != nullptr; return fail(FJGPU_ENOMEM, "ray queue overflow: lower the batch_tiles option"); }
-        if (launched_next && hc.next_count) { acc.trace_launches++; acc.closest_launches++; }       // (a walk of no rays is not counted ...
-        else if (launched_next) spans.pop_back();                                                   //  ... and not timed: its span was the last one recorded)
-        if (hc.light_count) {
-          // shading has completed (the host just synchronised with it): no event needed.
-          // The queue holds hc.shadow_count entries so far (exact when the shadow work runs on
-          // this stream, a lower bound otherwise: then the host-side bound is kept).
-          if (sst == st) sq_bound = hc.shadow_count;
-          uint32_t b = 0;
-          bool bound_is_exact = sst == st;
-          while (b < hc.light_count) {
-            const uint64_t room = sq_cap > (uint64_t) sq_bound + sq_pad ? sq_cap - sq_bound - sq_pad : 0;
-            uint32_t can = (uint32_t) std::min<uint64_t>(room / nl_q, hc.light_count - b);
-            if (can < hc.light_count - b && !bound_is_exact && sst == st) {
-              // the bound assumed that every (record, light) pair survived the cull: ask the
-              // device how full the queue really is before paying for a traversal launch
-              uint32_t used = 0;
-              if (hipMemcpyAsync(&used, &sc->d_cnt->shadow_count, sizeof(used), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-              sq_bound = used;
-              bound_is_exact = true;
-              continue;
-            }
-            if (can == 0 || (can < hc.light_count - b && can < (1u << 16))) {
-              // not worth a light-loop launch of its own: empty the queue first (an empty queue
-              // that still cannot take one record's rays takes them one record at a time)
-              if (sq_bound > 0) { e = flush_shadow(Sl); if (e) return e; continue; }
-              if (can == 0) can = 1;
-            }
-            acc.light_loop_launches++;
-            e = timed(sst, &acc.light_loop_ms, [&]() {
-              return launch_shadow_cull(sst, Sl, swp, sc->d_lrecs[lb], b, b + can, sc->d_accum, sc->d_squeue, sc->d_cnt, (int) sc->count_events,
-                  sst != st ? FJ_OVERLAP_CULL_BLOCKS : 0);
-            });
-            if (e) return e;
-            sq_bound += (uint64_t) can * nl_q + sq_pad;      // worst case: every pair survives, every wave leaves a padded chunk
-            bound_is_exact = false;
-            sq_dirty = true;
-            b += can;
-          }
-          if (sst != st) { (void) hipEventRecord(sc->ev_shadow_done[lb], sst); shadow_pending[lb] = true; }
-          // overlap: the shadow rays of level 0 -- most of a frame's -- are walked NOW, on the shadow stream, while the main stream runs the
-          // deeper levels' closest-hit walks, which are a few long rays each (a launch of its own per level, latency bound): the big walk hides them
-          // (early_shadow = k: the queue is flushed after level k - 1's light loops -- 2: levels 0 and 1, nearly all of a frame's shadow rays, are walked
-          //  beside the closest-hit walks of levels >= 2, which are a few long rays each)
-          if (sst != st && sc->early_shadow > 0 && level == (int) sc->early_shadow - 1 && can_emit && hc.next_count) { e = flush_shadow(Sl); if (e) return e; }
-        }
-        if (hc.next_count) {
-          if (!can_emit) return fail(FJGPU_EINVAL, "ray recursion deeper than the depth limits allow");
-          walk_launched = launched_next;
-          e = process(level + 1, hc.next_count);
-          if (e) return e;
-        }
-      }
-      return 0;
-    };
-    // the filter (and the adaptive sampler's decisions) need every shadow contribution so far
-    auto finish_shadow = [&]() -> int {
-      DScene Sf = S; Sf.lrec_hair = nullptr;
-      const int fe = flush_shadow(Sf);
-      if (fe) return fe;
-      if (sst != st) { (void) hipEventRecord(sc->ev_shadow_done[0], sst); shadow_pending[0] = true; }
-      for (int k = 0; k < FJ_LREC_BUFS; k++) if (shadow_pending[k] && sst != st) { (void) hipStreamWaitEvent(st, sc->ev_shadow_done[k], 0); shadow_pending[k] = false; }
-      return 0;
-    };
-    if (!adaptive) {
-      rc = process(0, n_samples);
-      if (rc) break;
-      rc = finish_shadow();
-      if (rc) break;
-    } else {
-      // AdaptiveGridSampler level by level (fjgpu_dev_adaptive.h): points -> wavefront -> decisions
-      ap.cells0 = cell_off;
-      (void) hipMemsetAsync(sc->d_apstate, 0, (size_t) n_samples, st);
-      (void) hipMemsetAsync(sc->d_acells, 0, (size_t) cell_off * (((((size_t) 1) << (2 * (ap.D + 1))) - 1) / 3), st);
-      rc = timed(st, &acc.gen_ms, [&]() { return launch_adaptive_uv(st, ap, sc->d_tiles, nb, max_ts, sc->d_jit, sc->d_suv); });
-      for (int level = 0; level <= ap.D && rc == 0; level++) {
-        ap.level = level;
-        (void) hipMemsetAsync(&sc->d_cnt->cam_count, 0, sizeof(uint32_t), st);
-        const uint32_t max_pts = (uint32_t) ((max_w0 << level) + 1) * (uint32_t) ((max_h0 << level) + 1);
-        rc = timed(st, &acc.gen_ms, [&]() {
-          return launch_adaptive_points(st, S, ap, sc->d_tiles, nb, max_pts, sc->d_acells, sc->d_suv, sc->d_accum, sc->d_apstate,
-              sc->d_aseen, sc->levels[0].rays, sc->levels[0].paths, sc->d_cnt);
-        });
-        if (rc) break;
-        DCounters hc;
-        if (hipMemcpyAsync(&hc, sc->d_cnt, sizeof(hc), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = -1; break; }
-        if (hc.overflow) { rc = fail(FJGPU_ENOMEM, "camera ray queue overflow in the adaptive sampler"); break; }
-        acc.rays.camera += hc.cam_count;
-        if (hc.cam_count) {
-          rc = process(0, hc.cam_count);
-          if (rc) break;
-          rc = finish_shadow();
-          if (rc) break;
-        }
-        rc = timed(st, &acc.resolve_ms, [&]() {
-          return launch_adaptive_decide(st, ap, sc->d_tiles, nb, (uint32_t) (max_w0 << level) * (uint32_t) (max_h0 << level),
-              sc->d_acells, sc->d_accum, sc->d_apstate, sc->d_aseen);
-        });
-      }
-      if (rc) break;
-      rc = timed(st, &acc.resolve_ms, [&]() {
-        return launch_adaptive_fill(st, ap, sc->d_tiles, nb, max_ts, sc->d_acells, sc->d_accum, sc->d_apstate, sc->d_aseen, sc->d_afinal);
-      });
-      if (rc) break;
-    }
-    rc = timed(st, &acc.resolve_ms, [&]() {
-      return launch_resolve(st, rp, sc->d_tiles, nb, max_px, sc->d_suv, sc->d_accum, adaptive ? sc->d_afinal : nullptr, d_fb);
-    });
-    if (rc) break;
-    // fjgpu_render_tiles_variance: the same samples once more, while the batch still holds them
-    if (sv) {
-      rc = timed(st, &acc.resolve_ms, [&]() {
-        return launch_sample_variance(st, rp, sc->d_tiles, nb, max_px, sc->d_suv, sc->d_accum, sv->albedo, sv->albedo_floor, sv->variance);
-      });
-      if (rc) break;
-    }
-    DCounters hc;
-    if (hipMemcpyAsync(&hc, sc->d_cnt, sizeof(hc), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = -1; break; }
-    if (hc.overflow) { sc->split_overflowed = S.shadow_join != nullptr; rc = fail(FJGPU_ENOMEM, "wavefront queue overflow: lower the batch_tiles option"); break; }
-    acc.rays.shadow += hc.rays[CXT_SHADOW_RAY];
-    acc.rays.diffuse += hc.rays[CXT_DIFFUSE_RAY];
-    acc.rays.reflect += hc.rays[CXT_REFLECT_RAY];
-    acc.rays.refract += hc.rays[CXT_REFRACT_RAY];
-    acc.nodes_visited += hc.nodes;
-    acc.prims_tested += hc.prims;
-    acc.insts_tested += hc.insts;
-    acc.rays_traced += hc.traced;
-    acc.shadow_traversed += hc.squeued;
-    acc.shadow_nodes += hc.sh_nodes; acc.shadow_prims += hc.sh_prims; acc.shadow_insts += hc.sh_insts;
-    sc->stack_peak_closest = std::max(sc->stack_peak_closest, hc.stack_peak);
-    sc->stack_peak_shadow = std::max(sc->stack_peak_shadow, hc.sh_stack_peak);
-    sc->hull_verdicts += hc.hull_settled;
-    acc.batches++;
-    if (sc->batch_fn) {
-      // (the stream was synchronised above: the batch's pixels are final in d_fb)
-      const std::vector<int32_t> bids(ids.begin() + (long) b0, ids.begin() + (long) b0 + nb);
-      if (sc->batch_fn(sc->batch_user, sc->device, bids.data(), nb)) { acc.interrupted = 1; break; }
-    }
-  }
-  (void) hipEventRecord(ev_all[1], st);
-  hipError_t se = hipStreamSynchronize(st);
-  if (sst != st) { const hipError_t s2 = hipStreamSynchronize(sst); if (se == hipSuccess) se = s2; }
-  if (rc == 0 && se == hipSuccess) {
-    (void) hipEventElapsedTime(&ms, ev_all[0], ev_all[1]);
-    acc.total_ms = ms;
-    for (const Span &sp : spans)
-      if (hipEventElapsedTime(&ms, sc->ev_pool[sp.a], sc->ev_pool[sp.b]) == hipSuccess) *sp.bucket += ms;
-    acc.closest_ms += acc.sort_ms;       // the sort is part of what the closest-hit side costs
-    acc.trace_ms = acc.closest_ms + acc.light_loop_ms + acc.shadow_walk_ms;
-  }
-  if (rc > 0 || rc == -1) return fail(FJGPU_ENODEV, std::string("HIP failure in the wavefront loop: ") + hipGetErrorString(hipGetLastError()));
-  if (rc) return rc;
-  if (se != hipSuccess) return fail(FJGPU_ENODEV, std::string("stream synchronize: ") + hipGetErrorString(se));
-  if (stats) *stats = acc;
-  return 0;
 }
 
 // One frame on G devices of this process: the reference's worker pool (execute_rendering,
@@ -2210,9 +1323,7 @@ int fjgpu_render_frame_multi(fjgpu_scene *const *scenes, int n_scenes, const fj_
   std::vector<fjgpu::TileRect> all;
   fjgpu::GenerateTiles(*r, &all);
   std::vector<int32_t> ids;
-  if (tile_ids) ids.assign(tile_ids, tile_ids + std::max(0, n_tiles));
-  else for (size_t i = 0; i < all.size(); i++) ids.push_back((int32_t) i);
-  for (int32_t id : ids) if (id < 0 || id >= (int32_t) all.size()) return fail(FJGPU_EINVAL, "tile id out of range");
+  if (const int e = listed_tiles(tile_ids, n_tiles, all.size(), &ids)) return e;
   const int G = n_scenes;
   const size_t npx = (size_t) r->xres * r->yres;
   const int tile_px = r->tile_w * r->tile_h;
@@ -2404,15 +1515,13 @@ int fjgpu_trace(fjgpu_scene *sc, int group, int n, const double *rays, double *o
     if (out_uv) { out_uv[2 * i] = h[i].inst >= 0 ? h[i].u : 0; out_uv[2 * i + 1] = h[i].inst >= 0 ? h[i].v : 0; }
   }
   sc->stack_peak_closest = sc->stack_peak_shadow = 0;
+  DCounters hc;
   if (stats || sc->count_events) {
-    DCounters hc;
     HIP_TRY(hipMemcpy(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost));
     sc->stack_peak_closest = hc.stack_peak;
   }
   if (stats) {
     std::memset(stats, 0, sizeof(*stats));
-    DCounters hc;
-    HIP_TRY(hipMemcpy(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost));
     stats->nodes_visited = hc.nodes; stats->prims_tested = hc.prims; stats->insts_tested = hc.insts; stats->rays_traced = hc.traced;
     stats->trace_ms = ms; stats->total_ms = ms; stats->trace_launches = 1;
   }
@@ -2441,33 +1550,15 @@ static int aov_setup(fjgpu_scene *sc, const fj_render_desc *r, const char *who, 
   if (sc->S.has_motion) return fail(FJGPU_EUNSUPPORTED, std::string(who) + ": a scene with motion (time-sampled transforms or vertex velocities) is not supported (static scenes only)");
   fjgpu::GenerateTiles(*r, &a->all);
   fjgpu::SamplerMargin(*r, a->margin);
-  GenParams &gp = a->gp;
-  gp.rate_x = r->rate_x; gp.rate_y = r->rate_y; gp.margin_x = a->margin[0]; gp.margin_y = a->margin[1];
-  gp.udelta = 1. / (r->rate_x * r->xres);
-  gp.vdelta = 1. / (r->rate_y * r->yres);
-  gp.jitter = r->jitter;
-  gp.jittered = r->jitter > 0 ? 1 : 0;
-  gp.pad = 0;
-  // camera (Renderer::preprocess_camera + Camera::compute_uv_size), as render_tiles_once sets it
+  a->gp = gen_params(r, a->margin);
   a->S = sc->S;
-  const double aspect = r->xres / (double) r->yres;
-  a->S.cam_uv_size[1] = fjgpu::CameraUvSizeY(sc->cam_fov);
-  a->S.cam_uv_size[0] = a->S.cam_uv_size[1] * aspect;
+  camera_uv_size(sc->cam_fov, r, a->S.cam_uv_size);
   a->S.time_start = r->time_start; a->S.time_end = r->time_end;
   a->S.lrec_hair = nullptr;
   a->S.cam_uv = nullptr; a->S.cam_tk = nullptr; a->S.cam_slot0 = 0;
   a->S.trace_ranges = nullptr; a->S.trace_n_dev = nullptr; a->S.ray_perm = nullptr;
   a->S.shadow_join = nullptr;
   return 0;
-}
-static TileDesc aov_tile(const fjgpu_scene *sc, const fj_render_desc *r, const fjgpu::TileRect &t, const int *margin, uint32_t sample_offset)
-{
-  TileDesc d;
-  d.xmin = t.xmin; d.ymin = t.ymin; d.xmax = t.xmax; d.ymax = t.ymax; d.id = fjgpu::SeededTileId(t.id, (unsigned) sc->sampler_seed);
-  d.nx = r->rate_x * (t.xmax - t.xmin) + 2 * margin[0];
-  d.ny = r->rate_y * (t.ymax - t.ymin) + 2 * margin[1];
-  d.sample_offset = sample_offset; d.cell_offset = 0; d.pad = 0;
-  return d;
 }
 
 // the body of fjgpu_render_aov and fjgpu_render_aov_albedo: one camera-ray generation and one closest-hit walk per batch, then k_aov_reduce
@@ -2486,10 +1577,8 @@ static int render_aov_body(const char *who_, fjgpu_scene *sc, const fj_render_de
   HIP_TRY(hipSetDevice(sc->device));
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
 
-  std::vector<int> ids;
-  if (tile_ids) ids.assign(tile_ids, tile_ids + n_tiles);
-  else for (size_t i = 0; i < A.all.size(); i++) ids.push_back((int) i);
-  for (int id : ids) if (id < 0 || id >= (int) A.all.size()) return fail(FJGPU_EINVAL, "tile id out of range");
+  std::vector<int32_t> ids;
+  if (const int e = listed_tiles(tile_ids, n_tiles, A.all.size(), &ids)) return e;
   fjgpu_stats acc;
   std::memset(&acc, 0, sizeof(acc));
   if (ids.empty()) { if (stats) *stats = acc; return 0; }
@@ -2502,7 +1591,7 @@ static int render_aov_body(const char *who_, fjgpu_scene *sc, const fj_render_de
   size_t cap_samples = 0, tab_len = 0;
   for (size_t k = 0; k < ids.size(); k++) {
     const fjgpu::TileRect &t = A.all[ids[k]];
-    TileDesc d = aov_tile(sc, r, t, A.margin, 0);
+    TileDesc d = fixed_grid_tile(sc, r, t, A.margin, 0);
     const size_t ts = (size_t) d.nx * (size_t) d.ny;
     if (ts > 0x7fffffffu) return fail(FJGPU_EINVAL, who + ": a tile of more than 2^31 samples: lower the tilesize");
     if (batches.empty() || batches.back().n >= 65535 || (size_t) batches.back().samples + ts > limit) batches.push_back(Batch{k, 0, 0u, 0u, 0});
@@ -2646,7 +1735,7 @@ int fjgpu_camera_samples(fjgpu_scene *sc, const fj_render_desc *r, int tile_id, 
   AovSetup A;
   if (const int e = aov_setup(sc, r, "fjgpu_camera_samples", &A)) return e;
   if (tile_id < 0 || tile_id >= (int) A.all.size()) return fail(FJGPU_EINVAL, "tile id out of range");
-  const TileDesc d = aov_tile(sc, r, A.all[tile_id], A.margin, 0);
+  const TileDesc d = fixed_grid_tile(sc, r, A.all[tile_id], A.margin, 0);
   const size_t n = (size_t) d.nx * (size_t) d.ny;
   if (n > 0x7fffffffu) return fail(FJGPU_EINVAL, "fjgpu_camera_samples: a tile of more than 2^31 samples");
   if (cap == 0) return (int) n;
@@ -2713,10 +1802,7 @@ int fjgpu_scene_view(const fjgpu_scene *sc, const fj_render_desc *r, fjgpu_view 
   double M[16], Minv[16];
   fjgpu::MakeTransform(sc->camera.xform, 0, M, Minv);
   std::memcpy(out->world_to_camera, Minv, sizeof(out->world_to_camera));
-  // (Renderer::preprocess_camera + Camera::compute_uv_size), as render_tiles_once sets it
-  const double aspect = r->xres / (double) r->yres;
-  out->uv_size[1] = fjgpu::CameraUvSizeY(sc->cam_fov);
-  out->uv_size[0] = out->uv_size[1] * aspect;
+  camera_uv_size(sc->cam_fov, r, out->uv_size);
   out->xres = r->xres; out->yres = r->yres;
   return 0;
 }

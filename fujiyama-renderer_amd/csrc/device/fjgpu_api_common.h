@@ -1,5 +1,6 @@
-// fjgpu_api_common.h -- what the translation units behind the C ABI of libfjgpu.so share (fjgpu_api.hip: entry points that take a
-// fjgpu_scene; fjgpu_image_api.hip: entry points that take only buffers): the error return, HIP_TRY and transient device buffers.
+// fjgpu_api_common.h -- what the translation units behind the C ABI of libfjgpu.so share (fjgpu_api.hip and fjgpu_frame.hip: entry
+// points that take a fjgpu_scene, whose record is fjgpu_scene.h; fjgpu_image_api.hip: entry points that take only buffers): the error
+// return, HIP_TRY and transient device buffers.
 #ifndef FJGPU_API_COMMON_H
 #define FJGPU_API_COMMON_H
 

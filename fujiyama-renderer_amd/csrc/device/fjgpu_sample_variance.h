@@ -1,5 +1,5 @@
 // fjgpu_sample_variance.h -- launcher of the sample-variance kernel (fjgpu_sample_variance.hip); the C entry point
-// fjgpu_render_tiles_variance is in fjgpu_api.hip, beside the beauty pass whose batches it reads
+// fjgpu_render_tiles_variance is in fjgpu_frame.hip, beside the beauty pass whose batches it reads
 #ifndef FJGPU_SAMPLE_VARIANCE_H
 #define FJGPU_SAMPLE_VARIANCE_H
 
